@@ -2,7 +2,13 @@
 """bench.py -- BASELINE.json's metric on MI355X:
    "train interactions/sec + eval users/sec (full-catalog top-K@20), 1/2/4/8 GPU".
 
-  python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]   (N>1: launched by torch.distributed.run)
+
+A plain run sets up, runs W warmup steps, times exactly K steps, writes what the last of them computed if
+--dump-outputs is given, and prints the line (`value`, `ms_per_step`, `timed_regions`, `last_losses`).  --full adds
+every other leg described below: per-kernel events and rooflines, the out-of-cache Adam pass, the sampler-inclusive
+end-to-end leg, the evaluator under both candidate filters, the CPU baselines and, at N > 1, the collective timing
+and the configs[4] leg.
 
 A "step" is one pass of the training hot path (gather + dots + counterfactual
 branches + (B,B) BCE + gradients + TF-style dense Adam) over one batch of B
@@ -26,11 +32,17 @@ the item catalogue across the ranks and exchanges per-shard top-K with one RCCL
 all-gather.
 
 Batches arrive as a sampler emits them (NOT ordered by item): the step groups its
-batch on the device, inside the timed region.  The K-step region is repeated
-(each repetition bracketed by barrier + synchronize, exactly K steps) until about
-60 ms have been timed and the MEDIAN repetition is reported: 20 steps are < 1 ms.
+batch on the device, inside the timed region.  The timed region is exactly K steps,
+bracketed by barrier + synchronize; --regions R repeats it R times and reports the
+MEDIAN repetition (--regions 0: as many as fit in about 60 ms).
 
-Rank 0 prints ONE JSON line.  Extra objects: `roofline` = the launch with the
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last one handed
+its caller -- the step's losses and the updated tables -- as DIR/<name>.npy in
+float32, at most 64 MB in all (above that, a fixed seeded sample of each table's
+rows).  Inputs are a function of the arguments alone, so two builds can be
+compared output for output.
+
+Rank 0 prints ONE JSON line.  Extra objects (--full): `roofline` = the launch with the
 largest time per step inside the timed region (HIP-event timed on the launch
 stream; for the default workload the (B,B) launch that carries the dense Adam
 pass), `roofline_step` (whole step, SURVEY.md 8d bytes / ms_per_step),
@@ -92,14 +104,52 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--pos", default="zipf", choices=["zipf", "uniform"], help="positive-item distribution (diagnostic)")
     ap.add_argument("--no-eval", action="store_true", help="skip the evaluator leg (diagnostic)")
-    ap.add_argument("--regions", type=int, default=0, help="number of timed K-step regions (0 = as many as fit in ~60 ms); the median is reported")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="number of timed K-step regions, the median reported (default 1: exactly --steps timed steps; 0 = as "
+                         "many as fit in ~60 ms)")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beyond the headline: per-kernel events and rooflines, the out-of-cache Adam pass, the end-to-end "
+                         "leg, the evaluator, the CPU baselines, N > 1: the collective timing and the configs[4] leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's losses and updated tables as DIR/<name>.npy (float32)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the sampler-inclusive end-to-end leg (diagnostic)")
     ap.add_argument("--no-defer", action="store_true", help="complete every step's Adam pass inside the step instead of under the next step's (B,B) kernel (diagnostic)")
     ap.add_argument("--through-cli-test", action="store_true",
-                    help="also time macr_mf/train.py::test() itself (tools/cli_test_cost.py in a subprocess: a synthetic dataset of the "
+                    help="with --full: also time macr_mf/train.py::test() itself (tools/cli_test_cost.py in a subprocess: a synthetic dataset of the "
                          "workload's shapes through the MF loader, the CLI's own call) -> `cli_test` in the line")
     ap.add_argument("--presorted", action="store_true", help="feed batches already ordered by positive item (diagnostic; the step orders its batch on the device either way)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: tensor} -> path/<name>.npy in float32 (float64 stays float64).  Above DUMP_LIMIT_BYTES in all,
+    every table keeps the same share of its rows, chosen by np.random.RandomState(0) and written in ascending order: the same
+    rows whatever the build."""
+    os.makedirs(path, exist_ok=True)
+    size = lambda t: t.numel() * (8 if t.dtype == torch.float64 else 4)
+    tables = [n for n, t in arrays.items() if t.dim() >= 2 and t.shape[0] > 1]
+    keep = 1.0
+    if sum(size(t) for t in arrays.values()) > DUMP_LIMIT_BYTES:
+        rest = sum(size(t) for n, t in arrays.items() if n not in tables)
+        keep = (DUMP_LIMIT_BYTES - rest) / float(sum(size(arrays[n]) for n in tables))
+    for name, t in arrays.items():
+        t = t.detach()
+        if keep < 1.0 and name in tables:
+            rows = np.sort(np.random.RandomState(0).choice(t.shape[0], max(1, int(t.shape[0] * keep)), replace=False))
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        a = t.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False))
+
+
+def region_counts(args, first_s, target_s, cap, dev):
+    """(timed regions to run, the automatic count): --regions R, default 1; 0 = repeat the K-step region until about
+    target_s seconds are on the clock (at most cap), the count agreed over the ranks"""
+    from macr_amd import sharding
+    n_auto = int(sharding.max_over_ranks(float(min(cap, max(1, round(target_s / max(first_s, 1e-6))))), dev))
+    return (n_auto if args.regions == 0 else (args.regions or 1)), n_auto
 
 
 def algorithmic_bytes(kernel, cfg, B):
@@ -167,20 +217,49 @@ def bench_config4(args, rank, world, dev, emit=True):
         return out
     run_steps(args.warmup, 0)
 
+    last_out = [None]
+
     def timed_region():
         barrier(); torch.cuda.synchronize()
         t0 = time.perf_counter()
-        run_steps(args.steps, args.warmup)
+        last_out[0] = run_steps(args.steps, args.warmup)
         model.flush()               # lazy dense Adam: the region ends with every row at its last step (the tables a reader would see)
         torch.cuda.synchronize(); barrier()
         return sharding.max_over_ranks(time.perf_counter() - t0, dev)
     regions = [timed_region()]
-    n_rep = args.regions if args.regions > 0 else int(min(50, max(1, round(0.25 / max(regions[0], 1e-6)))))
-    n_rep = int(sharding.max_over_ranks(float(n_rep), dev))
+    n_rep, _ = region_counts(args, regions[0], 0.25, 50, dev)
     regions += [timed_region() for _ in range(n_rep - 1)]
     elapsed = float(np.median(regions))
     ms_per_step = 1e3 * elapsed / args.steps
     value = B * args.steps / elapsed
+    if emit and rank == 0 and args.dump_outputs:          # (this rank's rows of the one model)
+        dump_outputs(args.dump_outputs, {"losses": last_out[0], "P": model.P, "Q": model.Q, "w": model.w, "wu": model.wu})
+    line = {"metric": "train interactions/sec + eval users/sec (full-catalog top-K@20)",
+            "value": value, "unit": "interactions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic"}
+    config = {"workload": "configs[4]: synthetic %d users x %d items, MACR-MF rubibceboth d=%d batch=%d c=%g; ONE model, "
+                          "rows sharded over %d rank(s), row r on rank r %% W (training), item-sharded evaluation of %d query users"
+                          % (n_users, n_items, d, B, c, world, args.c4_eval_users),
+              "parallelism": "row-sharded x%d: %s; evaluation: all-reduce of the query rows + one all-gather of per-shard "
+                             "top-K" % (world, ("split step -- all-to-all of the 3B/W rows a rank's slice needs, all-reduces of the "
+                                                "forward scalars, the (B,B) partials and the branch-vector partials, all-to-all of the "
+                                                "gradient rows back to their owners") if (world > 1 and model.split) else
+                                        ("all-reduce of the batch's 3B rows (%.1f MB) + all-reduce of the (B,B) partials + broadcast "
+                                         "of the branch-vector partials per step" % (3 * B * d * 4 / 1e6))),
+              "global_batch": B}
+    timed_regions = {"n": len(regions), "reported": "median", "min_ms_per_step": 1e3 * min(regions) / args.steps,
+                     "max_ms_per_step": 1e3 * max(regions) / args.steps}
+    if emit and not args.full:
+        last = last_out[0].cpu().numpy()
+        if not np.isfinite(last).all():
+            raise SystemExit("ERROR: loss is nan.")
+        if rank == 0:
+            print(json.dumps(dict(line, eval_users_per_s=None, config=config, lazy_adam_period=model.lazy_period,
+                                  timed_regions=timed_regions, last_losses=[float(x) for x in last])))
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return None
     last = run_steps(1, 0).cpu().numpy()
     if not np.isfinite(last).all():
         raise SystemExit("ERROR: loss is nan.")
@@ -337,21 +416,8 @@ def bench_config4(args, rank, world, dev, emit=True):
                "sample": "%d steps of the C port (fast build; B=%d, d=%d) on tables of 1/64 of the rows (%d + %d): the dense Adam "
                          "pass of the full tables would be 64x that part of a step" % (n_cpu, B, d, nu, ni)}
     if rank == 0:
-        out = {"metric": "train interactions/sec + eval users/sec (full-catalog top-K@20)",
-               "value": value, "unit": "interactions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-               "dtype": "f32", "data": "synthetic", "eval_users_per_s": eval_out.get("eval_users_per_s"),
-               "config": {"workload": "configs[4]: synthetic %d users x %d items, MACR-MF rubibceboth d=%d batch=%d c=%g; ONE model, "
-                                      "rows sharded over %d rank(s), row r on rank r %% W (training), item-sharded evaluation of %d query users"
-                                      % (n_users, n_items, d, B, c, world, args.c4_eval_users),
-                          "parallelism": "row-sharded x%d: %s; evaluation: all-reduce of the query rows + one all-gather of per-shard "
-                                         "top-K" % (world, ("split step -- all-to-all of the 3B/W rows a rank's slice needs, all-reduces of the "
-                                                            "forward scalars, the (B,B) partials and the branch-vector partials, all-to-all of the "
-                                                            "gradient rows back to their owners") if (world > 1 and model.split) else
-                                                    ("all-reduce of the batch's 3B rows (%.1f MB) + all-reduce of the (B,B) partials + broadcast "
-                                                     "of the branch-vector partials per step" % (3 * B * d * 4 / 1e6))),
-                          "global_batch": B},
-               "rows_per_rank": rows_local, "bytes_per_rank": 4.0 * d * rows_local * 4 + 4.0 * rows_local, "lazy_adam_period": model.lazy_period,
+        out = dict(line, eval_users_per_s=eval_out.get("eval_users_per_s"), config=config)
+        out.update({"rows_per_rank": rows_local, "bytes_per_rank": 4.0 * d * rows_local * 4 + 4.0 * rows_local, "lazy_adam_period": model.lazy_period,
                "lazy_adam_note": None if model.lazy_period <= 1 else
                "every timed region ends with a flush (all rows at the last step); a region shorter than ~4 periods (%d steps) never reaches the "
                "pass's steady lag and reads faster than training does -- quote --steps >= %d" % (4 * model.lazy_period, 4 * model.lazy_period),
@@ -362,9 +428,8 @@ def bench_config4(args, rank, world, dev, emit=True):
                            "(3,B,d) buffer the replicated step all-reduces (a ring moves ~2x that per rank)"},
                "collectives_ms": coll, "kernels": kern, "roofline": roofline,
                "roofline_step": roofline_step,
-               "timed_regions": {"n": len(regions), "reported": "median", "min_ms_per_step": 1e3 * min(regions) / args.steps,
-                                 "max_ms_per_step": 1e3 * max(regions) / args.steps},
-               "cpu_baseline": cpu, "last_losses": [float(x) for x in last]}
+               "timed_regions": timed_regions,
+               "cpu_baseline": cpu, "last_losses": [float(x) for x in last]})
         out.update(eval_out)
         if not emit:
             return out
@@ -418,8 +483,7 @@ def bench_lgcn(args, rank, world, dev):
         torch.cuda.synchronize(); barrier()
         return sharding.max_over_ranks(time.perf_counter() - t0, dev)
     regions = [timed_region()]
-    n_rep = args.regions if args.regions > 0 else int(min(100, max(1, round(0.1 / max(regions[0], 1e-6)))))
-    n_rep = int(sharding.max_over_ranks(float(n_rep), dev))
+    n_rep, _ = region_counts(args, regions[0], 0.1, 100, dev)
     regions += [timed_region() for _ in range(n_rep - 1)]
     elapsed = float(np.median(regions))
     ms_per_step = 1e3 * elapsed / args.steps
@@ -427,6 +491,29 @@ def bench_lgcn(args, rank, world, dev):
     losses = loss_log.cpu().numpy()
     if not np.isfinite(losses[: min(n_batches, args.steps)]).all():
         raise SystemExit("ERROR: loss is nan.")
+    last_k = (args.warmup + args.steps - 1) % n_batches
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"losses": loss_log[last_k], "T": state.T, "w": state.w, "wu": state.wu})
+    line = {"metric": "train interactions/sec + eval users/sec (full-catalog top-K@20)",
+            "value": value, "unit": "interactions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic", "nranks": world}
+    config = {"workload": "%s-shape MACR-LightGCN %s, %d layers [64,64], d=%d batch=%d c=%g (n_users=%d, n_items=%d, "
+                          "N=%d nodes, nnz=%d = 2*n_train, `pre` adjacency); synthetic graph (lognormal user degrees, Zipf "
+                          "items), Xavier tables, batches as sampled"
+                          % (args.workload, "bceboth" if kind == ops.LOSS_RUBIBCEBOTH else "bce", L, d, B, cfg["c"], n_u, n_i, N, nnz),
+              "parallelism": "replicas x%d (train) / item-sharded x%d + RCCL all-gather (eval)" % (world, world),
+              "global_batch": B * world}
+    timed_regions = {"n": len(regions), "each": "exactly %d steps, barrier+synchronize on both sides" % args.steps,
+                     "reported": "median", "min_ms_per_step": 1e3 * min(regions) / args.steps,
+                     "max_ms_per_step": 1e3 * max(regions) / args.steps}
+    last_losses = [float(x) for x in losses[last_k]]
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(dict(line, eval_users_per_s=None, config=config, timed_regions=timed_regions, last_losses=last_losses)))
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
     # per-kernel HIP events on the launch stream, calibrated against the un-instrumented region as in main()
     n_prof = 10
     ops.timing_begin()
@@ -630,21 +717,9 @@ def bench_lgcn(args, rank, world, dev):
                          % (n_fast, n_strict, n_torch, B, N, nnz, L, t_prop, n_ev, U),
                "eval_users_per_s": ev_impl["c_port_fast"], "eval_implementations": ev_impl}
     if rank == 0:
-        out = {"metric": "train interactions/sec + eval users/sec (full-catalog top-K@20)",
-               "value": value, "unit": "interactions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-               "dtype": "f32", "data": "synthetic", "nranks": world, "eval_users_per_s": eval_out.get("eval_users_per_s"),
-               "config": {"workload": "%s-shape MACR-LightGCN %s, %d layers [64,64], d=%d batch=%d c=%g (n_users=%d, n_items=%d, "
-                                      "N=%d nodes, nnz=%d = 2*n_train, `pre` adjacency); synthetic graph (lognormal user degrees, Zipf "
-                                      "items), Xavier tables, batches as sampled"
-                                      % (args.workload, "bceboth" if kind == ops.LOSS_RUBIBCEBOTH else "bce", L, d, B, cfg["c"], n_u, n_i, N, nnz),
-                          "parallelism": "replicas x%d (train) / item-sharded x%d + RCCL all-gather (eval)" % (world, world),
-                          "global_batch": B * world},
-               "timed_regions": {"n": len(regions), "each": "exactly %d steps, barrier+synchronize on both sides" % args.steps,
-                                 "reported": "median", "min_ms_per_step": 1e3 * min(regions) / args.steps,
-                                 "max_ms_per_step": 1e3 * max(regions) / args.steps},
-               "event_overhead_us_per_launch": overhead, "kernels": kern, "roofline": roofline, "roofline_step": roofline_step,
-               "cpu_baseline": cpu, "last_losses": [float(x) for x in losses[(args.warmup + args.steps - 1) % n_batches]]}
+        out = dict(line, eval_users_per_s=eval_out.get("eval_users_per_s"), config=config, timed_regions=timed_regions,
+                   event_overhead_us_per_launch=overhead, kernels=kern, roofline=roofline, roofline_step=roofline_step,
+                   cpu_baseline=cpu, last_losses=last_losses)
         out.update(eval_out)
         print(json.dumps(out))
     if world > 1:
@@ -888,7 +963,17 @@ def main():
         raise SystemExit("--gpus %d but WORLD_SIZE=%d: launch with --nproc-per-node %d (or without a launcher: bench.py "
                          "starts its own ranks)" % (args.gpus, world, args.gpus))
     if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs an MI355X (no CPU fallback for the HIP path)")
+        msg = "bench.py needs an MI355X (no CPU fallback for the HIP path)"
+        if world > 1:
+            # every rank says so before any of them exits: the launcher stops the other ranks as soon as one has failed
+            import datetime
+            print(msg, file=sys.stderr, flush=True)
+            os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+            torch.distributed.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+            raise SystemExit(1)
+        raise SystemExit(msg)
     # one process per GPU over RCCL; MACR_DIST_BACKEND=gloo lets several ranks share one GPU (test rig for the N>1 path)
     backend = os.environ.get("MACR_DIST_BACKEND", "nccl")
     local_rank = local_rank % torch.cuda.device_count() if backend == "gloo" else local_rank
@@ -949,9 +1034,8 @@ def main():
         return sharding.max_over_ranks(time.perf_counter() - t0, dev)
 
     regions = [timed_region()]
-    # a 20-step region is under a millisecond: repeat the SAME K-step region until ~60 ms are on the clock, report the median
-    n_rep = args.regions if args.regions > 0 else int(min(200, max(1, round(0.06 / max(regions[0], 1e-6)))))
-    n_rep = int(sharding.max_over_ranks(float(n_rep), dev))
+    # --regions 0: a 20-step region is under a millisecond; repeat the SAME K-step region until ~60 ms are on the clock
+    n_rep, n_auto = region_counts(args, regions[0], 0.06, 200, dev)
     regions += [timed_region() for _ in range(n_rep - 1)]
     elapsed = float(np.median(regions))
     ms_per_step = 1e3 * elapsed / args.steps
@@ -959,6 +1043,28 @@ def main():
     losses = loss_log.cpu().numpy()
     if not np.isfinite(losses[: min(n_batches, args.steps)]).all():
         raise SystemExit("ERROR: loss is nan.")
+    last_k = (args.warmup + args.steps - 1) % n_batches
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"losses": loss_log[last_k], "P": state.P, "Q": state.Q, "w": state.w, "wu": state.wu})
+    line = {"metric": "train interactions/sec + eval users/sec (full-catalog top-K@20)",
+            "value": value, "unit": "interactions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic"}
+    config = {"workload": "%s-shape MACR-MF %s d=%d batch=%d c=%g (n_users=%d, n_items=%d); synthetic "
+                          "Xavier tables, Zipf positives, batches as sampled (grouped on the device inside the step)" % (args.workload, args.train, d, B, cfg["c"],
+                                                             cfg["n_users"], cfg["n_items"]),
+              "parallelism": "replicas x%d (train) / item-sharded x%d + RCCL all-gather (eval)" % (world, world),
+              "global_batch": B * world}
+    timed_regions = {"n": len(regions), "each": "exactly %d steps, barrier+synchronize on both sides" % args.steps,
+                     "reported": "median", "min_ms_per_step": 1e3 * min(regions) / args.steps,
+                     "max_ms_per_step": 1e3 * max(regions) / args.steps}
+    last_losses = [float(x) for x in losses[last_k]]
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(dict(line, eval_users_per_s=None, config=config, timed_regions=timed_regions, last_losses=last_losses)))
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
 
     # ------------------------------------------------------------- per-kernel HIP-event timing (same stream)
     # Recording an event after every launch adds a fixed cost to each event-to-event interval (the un-instrumented
@@ -1093,7 +1199,7 @@ def main():
             state.flush()
         run_e2e(args.warmup)
         e2e = []
-        for _ in range(max(1, min(n_rep, 50))):
+        for _ in range(max(1, min(args.regions or n_auto, 50))):
             barrier(); torch.cuda.synchronize()
             t0 = time.perf_counter()
             run_e2e(args.steps)
@@ -1328,18 +1434,11 @@ def main():
         except Exception as e:                                     # noqa: BLE001
             cli_test = {"error": repr(e)[:200]}
     if rank == 0:
-        out = {
-            "metric": "train interactions/sec + eval users/sec (full-catalog top-K@20)",
-            "value": value, "unit": "interactions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
+        out = dict(line)
+        out.update({
             "eval_users_per_s": eval_users_per_s,
             "nranks": 1 if multi is None else multi["nranks"], "multi_gpu": multi,
-            "config": {"workload": "%s-shape MACR-MF %s d=%d batch=%d c=%g (n_users=%d, n_items=%d); synthetic "
-                                   "Xavier tables, Zipf positives, batches as sampled (grouped on the device inside the step)" % (args.workload, args.train, d, B, cfg["c"],
-                                                                      cfg["n_users"], cfg["n_items"]),
-                       "parallelism": "replicas x%d (train) / item-sharded x%d + RCCL all-gather (eval)" % (world, world),
-                       "global_batch": B * world},
+            "config": config,
             "eval": eval_summary,
             "sharded_figure": {"name": "eval_users_per_s", "value": eval_users_per_s, "scaling": "strong",
                                "note": "`value` counts N independent training replicas (these configs' step fits one GPU: "
@@ -1354,16 +1453,14 @@ def main():
             "eval_modes": None if ev_elapsed is None else ev_modes,
             "eval_ms_unseeded": None if ev_elapsed is None else ev_unseeded_ms,
             "eval_users": len(users), "eval_metrics": {k: float(v[0]) for k, v in ret.items()},
-            "timed_regions": {"n": len(regions), "each": "exactly %d steps, barrier+synchronize on both sides" % args.steps,
-                              "reported": "median", "min_ms_per_step": 1e3 * min(regions) / args.steps,
-                              "max_ms_per_step": 1e3 * max(regions) / args.steps},
+            "timed_regions": timed_regions,
             "step_kernel_us": step_kernel_us, "event_overhead_us_per_launch": event_overhead_us, "kernels": kern_avg,
             "roofline": roofline, "roofline_step": roofline_step, "roofline_aux": aux,
             "roofline_bxb": roofline_bxb(args.workload, B, kern_avg) if kind == ops.LOSS_RUBIBCEBOTH else None,
             "end_to_end": end_to_end, "cli_test": cli_test,
             "roofline_eval": roofline_eval, ("roofline_eval_" + (roofline_eval_bf16 or {}).get("filter", "bf16")): roofline_eval_bf16, "cpu_baseline": cpu,
-            "last_losses": [float(x) for x in losses[(args.warmup + args.steps - 1) % n_batches]],
-        }
+            "last_losses": last_losses,
+        })
         if c4_line is not None:
             # configs[4] in the same line: interactions/s of ONE model row-sharded over the ranks (strong scaling), its
             # per-step collectives and the item-sharded evaluation of 100 000 query users against 1 M items

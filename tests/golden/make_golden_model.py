@@ -19,7 +19,7 @@ does NOT pin (still "[TF-1.14 knowledge]"): tf.train.AdamOpti
 placement, the Xavier initialiser's stream, Eigen's fp32 sigmoid/log kernels and reduction order.
 
 Every case is run twice, in float32 (the reference's dtype) and in float64 (the value the fp32 run approximates).
-Only inputs and outputs are stored (tests/golden/G10_model_steps.npz); no reference text travels.
+Only inputs and outputs are stored (tests/golden/G10_model_steps_*.npz); no reference text travels.
 
 Usage:  python tests/golden/make_golden_model.py
 """
@@ -278,9 +278,15 @@ def main():
                     if dname == "f64" or np.ndim(v) == 0:
                         out["lgcn_%s/%s/%s/%s" % (tag, loss_name, dname, k)] = np.asarray(v)
     out["hyper"] = np.asarray([hyper["alpha"], hyper["beta"], hyper["decay"], hyper["batch_size"]], np.float64)
-    path = os.path.join(HERE, "G10_model_steps.npz")
-    np.savez_compressed(path, **out)
-    print("wrote %s (%d arrays, %.1f KB)" % (path, len(out), os.path.getsize(path) / 1024))
+    # in parts, each under the 1 MiB limit of a committed file; tests/helpers.py:golden_npz_parts merges every G10_model_steps_*.npz
+    parts = {}
+    for k, v in out.items():
+        top = k.split("/")[0]
+        parts.setdefault(top if top in ("mf_b", "lgcn_b") else "rest", {})[k] = v
+    for name, arrays in parts.items():
+        path = os.path.join(HERE, "G10_model_steps_%s.npz" % name)
+        np.savez_compressed(path, **arrays)
+        print("wrote %s (%d arrays, %.1f KB)" % (path, len(arrays), os.path.getsize(path) / 1024))
 
 
 if __name__ == "__main__":

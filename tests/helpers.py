@@ -13,6 +13,18 @@ def golden(half, dataset):
     return json.load(open(os.path.join(GOLD, "golden_%s_%s.json" % (half, dataset))))
 
 
+def golden_npz_parts(stem):
+    """{key: array} of every tests/golden/<stem>_*.npz: a fixture above the 1 MiB limit of a committed file is stored in parts
+    (tests/golden/make_golden_model.py writes them)"""
+    parts = sorted(f for f in os.listdir(GOLD) if f.startswith(stem + "_") and f.endswith(".npz"))
+    assert parts, "no %s_*.npz under %s" % (stem, GOLD)
+    out = {}
+    for f in parts:
+        with np.load(os.path.join(GOLD, f)) as z:
+            out.update((k, z[k]) for k in z.files)
+    return out
+
+
 def score_matrix(kind, n_users, n_items, seed):
     """Must stay identical to tests/golden/make_golden.py::score_matrix (frozen legacy RandomState)."""
     rs = np.random.RandomState(seed)

@@ -92,3 +92,25 @@ def test_bench_gpus_n_becomes_its_own_launcher():
         return                                           # (on a GPU box the -m gpu test runs the whole thing)
     assert r.returncode != 0
     assert r.stderr.count("bench.py needs an MI355X") >= 2, r.stderr[-3000:]
+
+
+def test_bench_dump_outputs_writes_float32_within_its_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array as <name>.npy in float32 (float64 kept); above the limit, the same seeded rows of
+    every table, in ascending order, whatever the call."""
+    import numpy as np
+    import torch
+    bench = load(os.path.join(REPO, "bench.py"), "bench_dump")
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 40_000)
+    P = torch.arange(1000 * 16, dtype=torch.float32).reshape(1000, 16)
+    arrays = {"losses": torch.tensor([1.0, 2.0, 3.0]), "P": P, "w": torch.ones(16, dtype=torch.float64)}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    got = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))}
+    assert set(got) == {"losses", "P", "w"}
+    assert got["losses"].dtype == np.float32 and got["P"].dtype == np.float32 and got["w"].dtype == np.float64
+    assert sum(v.nbytes for v in got.values()) <= 40_000 and 0 < got["P"].shape[0] < 1000
+    rows = got["P"][:, 0] / 16
+    assert (np.diff(rows) > 0).all() and np.array_equal(got["P"], P.numpy()[rows.astype(np.int64)])
+    assert np.array_equal(np.load(str(tmp_path / "b" / "P.npy")), got["P"])
+    bench.dump_outputs(str(tmp_path / "c"), {"P": P[:10]})                  # under the limit: the whole array
+    assert np.array_equal(np.load(str(tmp_path / "c" / "P.npy")), P[:10].numpy())

@@ -1,14 +1,14 @@
 """HIP training steps against G10 (-m gpu): losses and gradients computed by the reference's own loss-graph code
 (tests/golden/make_golden_model.py), through the C ABI.  Gradients are read off the first Adam step (m = 0.1 * g)."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
+from helpers import golden_npz_parts
+
 pytestmark = pytest.mark.gpu
 
-G10 = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "G10_model_steps.npz"))
+G10 = golden_npz_parts("G10_model_steps")
 ALPHA, BETA, DECAY, BS = (float(G10["hyper"][0]), float(G10["hyper"][1]), float(G10["hyper"][2]), int(G10["hyper"][3]))
 
 

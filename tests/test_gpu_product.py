@@ -354,7 +354,7 @@ def test_bench_two_ranks_share_one_gpu(tmp_path):
     The single-rank run is the reference for the eval metrics."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--workload", "addressa", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--eval-reps", "1",
+    common = ["--full", "--workload", "addressa", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--eval-reps", "1",
               "--regions", "1", "--no-e2e", "--eval-train-steps", "0"]   # same training steps in both runs: same model
     one = subprocess.run([sys.executable, "bench.py", "--gpus", "1"] + common, cwd=root, capture_output=True, text=True,
                          timeout=600)
@@ -374,6 +374,32 @@ def test_bench_two_ranks_share_one_gpu(tmp_path):
     assert a["nranks"] == 1 and "config4" not in a
     for k, v in a["eval_metrics"].items():            # same model (rank 0's), item-sharded: same ranking metrics
         assert abs(b["eval_metrics"][k] - v) <= 2e-3 * max(abs(v), 1e-3), (k, v, b["eval_metrics"][k])
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py --steps K --warmup W` times exactly K steps and prints the headline alone (the other legs are
+    --full's); --dump-outputs writes the last step's losses and tables in float32, the same from run to run."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = [], []
+    for r in range(2):
+        out = tmp_path / ("run%d" % r)
+        p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--workload", "addressa", "--steps", "7", "--warmup", "3",
+                            "--dump-outputs", str(out)], cwd=root, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines.append(json.loads(p.stdout.strip().splitlines()[-1]))
+        dumps.append({f[:-4]: np.load(str(out / f)) for f in os.listdir(str(out))})
+    a = lines[0]
+    assert a["steps"] == 7 and a["warmup"] == 3 and a["timed_regions"]["n"] == 1 and a["value"] > 0
+    assert abs(a["ms_per_step"] - 1e3 * 1024 / a["value"]) <= 1e-6 * a["ms_per_step"]
+    assert a["higher_is_better"] is True and a["dtype"] == "f32" and a["unit"] == "interactions/s"
+    assert not set(a) & {"kernels", "roofline", "roofline_eval", "end_to_end", "cpu_baseline", "eval"}
+    assert set(dumps[0]) == {"losses", "P", "Q", "w", "wu"}
+    assert dumps[0]["P"].shape == (13485, 64) and dumps[0]["Q"].shape == (744, 64)
+    assert all(v.dtype == np.float32 for v in dumps[0].values())
+    np.testing.assert_allclose(dumps[0]["losses"], a["last_losses"], rtol=1e-6)
+    for k, v in dumps[0].items():
+        np.testing.assert_allclose(dumps[1][k], v, rtol=1e-4, atol=1e-6, err_msg=k)
 
 
 def test_repair_round_continues_on_the_first_rounds_workspace(ops):

@@ -3,14 +3,13 @@ code (tests/golden/make_golden_model.py runs macr_mf/model.py and macr_lightgcn/
 functional tensorflow stand-in).  Pins oracle/macr_oracle.c's restatement of model.py:185-222 / :277-287 and
 LightGCN.py:288-309 / :415-429 / :495-532; tf.train.AdamOptimizer itself stays unpinned (TF absent), so gradients are
 read off the first Adam step, where m = (1 - beta1) * g exactly."""
-import os
-
 import numpy as np
 import pytest
 
 import oracle
+from helpers import golden_npz_parts
 
-G10 = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "G10_model_steps.npz"))
+G10 = golden_npz_parts("G10_model_steps")
 ALPHA, BETA, DECAY, BS = (float(G10["hyper"][0]), float(G10["hyper"][1]), float(G10["hyper"][2]), int(G10["hyper"][3]))
 KINDS = {"normalbce": oracle.LOSS_NORMALBCE, "rubibceboth": oracle.LOSS_RUBIBCEBOTH, "rubibce": oracle.LOSS_RUBIBCE}
 

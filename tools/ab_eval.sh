@@ -6,7 +6,7 @@ out=$1; shift
 for rep in 1 2; do
   for e in "$@"; do
     envs=""; [ "$e" != "-" ] && envs="$e"
-    line=$(env $envs python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-config4 ${AB_ARGS} 2>/dev/null | tail -1)
+    line=$(env $envs python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-config4 ${AB_ARGS} 2>/dev/null | tail -1)
     python - "$e" "$line" >> "$out" <<'PY'
 import json, sys
 e, line = sys.argv[1], sys.argv[2]

@@ -6,7 +6,7 @@ out=$1; shift
 for rep in 1 2 3; do
   for e in "$@"; do
     envs=""; [ "$e" != "-" ] && envs="$e"
-    line=$(env $envs python bench.py --no-cpu-baseline --no-eval --no-e2e ${AB_ARGS} 2>/dev/null | tail -1)
+    line=$(env $envs python bench.py --full --regions 0 --no-cpu-baseline --no-eval --no-e2e ${AB_ARGS} 2>/dev/null | tail -1)
     python - "$e" "$line" >> "$out" <<'PY'
 import json, sys
 e, line = sys.argv[1], sys.argv[2]

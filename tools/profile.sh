@@ -3,7 +3,7 @@
 # (FETCH_SIZE and WRITE_SIZE need separate passes: TCC has 4 slots, MI355X_MICROARCH.md "rocprofv3 PMC slots";
 # counters are never combined with sys/hip/hsa tracing).
 #   bash tools/profile.sh <tag> <command...>     -> gpurun_out/prof_<tag>/{trace,pmc_fetch,pmc_write,pmc_sq}
-# The default bench:  bash tools/profile.sh bench python $PWD/bench.py --steps 200 --warmup 20 --no-cpu-baseline
+# The default bench:  bash tools/profile.sh bench python $PWD/bench.py --full --steps 200 --warmup 20 --no-cpu-baseline
 set -x
 tag=$1; shift
 ROOT=$PWD
