@@ -39,13 +39,20 @@ extern "C" {
 #define MACR_E_WORKSPACE    -3   /* workspace too small                                         */
 #define MACR_E_LAUNCH       -4   /* hipLaunch / runtime failure                                 */
 
-#define MACR_ABI_VERSION     15
+#define MACR_ABI_VERSION     16
 
 /* loss kinds */
 #define MACR_LOSS_NORMALBCE   0  /* --train normalbce   macr_mf/model.py:277-287 ; --loss bce     LightGCN.py:415-429 */
 #define MACR_LOSS_RUBIBCEBOTH 1  /* --train rubibceboth macr_mf/model.py:185-222 ; --loss bceboth LightGCN.py:495-532 */
 #define MACR_LOSS_RUBIBCE     2  /* --train rubibce     macr_mf/model.py:158-183 : item branch only (MF only);
                                     the rubibceboth graph with sigmoid(e_u.w_user) := 1, w_user untouched        */
+#define MACR_LOSS_BPR         3  /* --train normal      macr_mf/model.py:264-275 (abi 16; MF only): -mean(log(sigmoid(p - n))),
+                                    no epsilon (margins below about -100 overflow fp32: loss +inf, gradient NaN, as in TF) */
+#define MACR_LOSS_BPR_LGCN    4  /* --loss bpr          LightGCN.py:398-413 (abi 16; LightGCN only):
+                                    -mean(log(1e-9 + sigmoid(sigmoid(p) - sigmoid(n)))), emb_loss on the ego rows      */
+/* NORMALBCE, BPR and BPR_LGCN are the PER-PAIR kinds: no (B,B) term and no branch vectors (w, w_user untouched).  Every
+ * entry point that takes NORMALBCE takes the per-pair kind of its model; every one that refuses NORMALBCE refuses them too,
+ * with the same error code. */
 
 /* score kinds */
 #define MACR_SCORE_NORMAL    0   /* batch_ratings      macr_mf/model.py:45  ; LightGCN.py:166 */
@@ -94,7 +101,7 @@ typedef struct macr_hyper {
  *
  *   u,i,j      (dev) int32[B]     sampled users / positive / negative items
  *   P,Q        (dev) fp32[n_users*d], fp32[n_items*d]  updated in place
- *   w,wu       (dev) fp32[d]      item / user branch vectors (rubibceboth only)
+ *   w,wu       (dev) fp32[d]      item / user branch vectors (rubibce / rubibceboth; may be NULL for NORMALBCE, BPR)
  *   m*,v*      (dev) Adam slots, same shapes, updated in place
  *   gP,gQ      (dev) fp32 same shape as P,Q: dense gradient scratch that MUST be
  *              all-zero on entry and is all-zero again on return (rows touched
@@ -105,12 +112,13 @@ typedef struct macr_hyper {
  *   losses     (dev) fp32[3] = {loss, mf_loss, reg_loss} of this step
  *   workspace  (dev) >= macr_mf_train_workspace_bytes(B, d) bytes, 256-B aligned
  *
+ * loss_kind: NORMALBCE, RUBIBCEBOTH, RUBIBCE or BPR.
  * d must be 32, 64, 128 or 256.  B >= 1.  No host synchronisation; safe to
  * capture into a hipGraph.
  *
  * flags = 0: the call is one complete step (P, Q, w, wu and the slots are up to
  * date in stream order when it returns).
- * Deferred mode (rubibceboth only): the step's pass over ALL rows of P and Q
+ * Deferred mode (rubibceboth, rubibce; the per-pair kinds: MACR_E_INVALID): the step's pass over ALL rows of P and Q
  * (tf.train.AdamOptimizer moves every row every step) is bound by HBM, the
  * (B,B) loss kernel by the VALU; neither depends on the other across a step
  * boundary, so consecutive steps can overlap them:
@@ -158,8 +166,8 @@ int macr_mf_train_flush(int loss_kind, int B, int d, int n_users, int n_items,
  * gradient scratch are range-sharded over W ranks (new: the reference keeps each table
  * in one tf.Variable, macr_mf/model.py:112-113; BASELINE configs[4] = 10 M x 1 M rows,
  * d = 128 on 8 GPUs, where the dense Adam pass alone streams 33.8 GB per step).
- * Same arithmetic as macr_mf_train_step (all loss kinds; NORMALBCE has no (B,B) term and no branch vectors:
- * macr_shard_forward only prepares indices, macr_shard_bxb is not called, *branch_bytes comes back 0); the three
+ * Same arithmetic as macr_mf_train_step (its loss kinds; the per-pair kinds NORMALBCE and BPR have no (B,B) term and no branch
+ * vectors: macr_shard_forward only prepares indices, macr_shard_bxb is not called, *branch_bytes comes back 0); the three
  * exchanges between the calls are the host's (torch.distributed / RCCL over xGMI,
  * macr_amd/sharded_train.py):
  *   macr_shard_gather    rows3[3][B][d] = the batch rows THIS rank owns, zero elsewhere      -> all-reduce(sum) rows3
@@ -191,6 +199,7 @@ int macr_shard_backward(int loss_kind, int B, int d, const float *rows3, const f
 /* The SPLIT step (branch losses): rank r runs forward and backward only for the positions [t0, t1) of the batch whose (B,B) row
  * blocks it evaluates (macr_shard_slice), on rows their owners sent it, and returns the gradient rows to the owners -- two
  * all-to-alls of 3B/W rows per rank instead of an all-reduce of 3B rows (macr_amd/sharded_train.py::RowShardedMF.step_split).
+ * Branch losses only: the per-pair kinds NORMALBCE and BPR -> MACR_E_UNSUPPORTED.
  *   macr_shard_forward_slice   rows3_slice (dev) fp32[3][n][d]: user / positive / negative rows of positions t0 .. t0+n-1; returns
  *                              a region of the workspace (zero outside the slice) whose SUM over the ranks is the forward state
  *                              of the whole batch -- sum it (one all-reduce) before macr_shard_bxb
@@ -255,7 +264,8 @@ typedef struct macr_lazy_adam {
     int       period;
 } macr_lazy_adam;
 
-/* macr_mf_train_step / macr_mf_train_flush with the lazy pass in place of the dense one (the (B,B) losses; same arguments +
+/* macr_mf_train_step / macr_mf_train_flush with the lazy pass in place of the dense one (the (B,B) losses -- the per-pair kinds:
+ * MACR_E_UNSUPPORTED from the step, MACR_E_INVALID from the flush, as from the dense forms; same arguments +
  * lazy; stampP / stampQ: uint32[n_users] / uint32[n_items]).  Use ONE form for all calls of a deferred sequence (from the
  * first MACR_STEP_DEFER call to the flush or the call that completes it): the step counter advances in every call of the
  * lazy form.  In deferred mode the pass riding in a step's (B,B) launch updates the rows of the previous and of the current
@@ -364,9 +374,9 @@ int macr_lgcn_propagate(int N, int d, int n_layers, const int32_t *rowptr, const
 
 /* One LightGCN training step.  Replaces sess.run([opt_X, loss_X, mf_loss_X,
  * emb_loss_X, reg_loss_X]) of macr_lightgcn/LightGCN.py:598-607: propagation,
- * gathers on the propagated table (:145-150), loss (:415-429 or :495-532) with
- * the regulariser on the ego rows (:525-527), dense gradients through the
- * propagation, Adam (:186 / :201).
+ * gathers on the propagated table (:145-150), loss (loss_kind NORMALBCE :415-429,
+ * RUBIBCEBOTH :495-532 or BPR_LGCN :398-413) with the regulariser on the ego rows
+ * (:525-527), dense gradients through the propagation, Adam (:186 / :201 / :178).
  *   T (dev) fp32[N*d] = [user_embedding ; item_embedding], updated in place
  *   mT,vT Adam slots;  workspace (dev) >= macr_lgcn_train_workspace_bytes(B,N,d,plan_host) bytes, ZERO-FILLED ONCE
  *          before its first use (the batch-row flags and the hub rows' arrival counters are zero

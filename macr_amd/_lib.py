@@ -11,14 +11,19 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MACR_HIP_LIB") or os.path.join(_HERE, "csrc", "libmacr_hip.so")
 
 OK, E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_LAUNCH = 0, -1, -2, -3, -4
-LOSS_NORMALBCE, LOSS_RUBIBCEBOTH, LOSS_RUBIBCE = 0, 1, 2
+LOSS_NORMALBCE, LOSS_RUBIBCEBOTH, LOSS_RUBIBCE, LOSS_BPR, LOSS_BPR_LGCN = 0, 1, 2, 3, 4
 STEP_DEFER, STEP_PENDING, STEP_LOSS_ONLY, STEP_DENSE_LAYERS = 1, 2, 4, 8
 SCORE_NORMAL, SCORE_RUBI_BOTH, SCORE_RUBI, SCORE_DIRECT_MINUS, SCORE_DIRECT_MINUS_BOTH = 0, 1, 2, 3, 4
 MAX_TOPK = 128
 MAX_TOPK_FUSED = 32
 MAX_SWEEP = 4
-ABI_VERSION = 15
+ABI_VERSION = 16
 LAZY_STATE_BYTES, LAZY_MAX_PERIOD = 1040, 64
+
+
+def is_pair_loss(kind):
+    """the per-pair loss kinds (normalbce, MF bpr, LightGCN bpr): no (B,B) term, no branch vectors, no deferred mode"""
+    return kind in (LOSS_NORMALBCE, LOSS_BPR, LOSS_BPR_LGCN)
 
 
 class MacrError(RuntimeError):

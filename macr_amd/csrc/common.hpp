@@ -111,6 +111,45 @@ __device__ __forceinline__ float sigmoid_acc(float x) { return 1.0f / (1.0f + ex
 __device__ __forceinline__ float dneglog_sig(float s, float eps) { return -((s * (1.0f - s)) / (s + eps)); }
 __device__ __forceinline__ float dneglog_1msig(float s, float eps) { return (s * (1.0f - s)) / ((1.0f - s) + eps); }
 
+// ---- per-pair losses (no (B,B) term, no branch vectors): the epilogue policies of k_pair_normal / k_pair_normal_stage --
+// term(p, n, invB, dp, dn): the pair's summand of B * mf_loss; dp, dn = d mf_loss / d p, d n.
+struct PairLossBCE {        // MACR_LOSS_NORMALBCE: -log(sig(p)+1e-9) - log(1-sig(n)+1e-9)      macr_mf/model.py:277-287
+    __device__ static __forceinline__ float term(float p, float n, float invB, float &dp, float &dn) {
+        const float eps = 1e-9f;
+        const float sp = sigmoid_acc(p), sn = sigmoid_acc(n);
+        dp = dneglog_sig(sp, eps) * invB; dn = dneglog_1msig(sn, eps) * invB;
+        return -logf(sp + eps) + -logf((1.0f - sn) + eps);
+    }
+};
+struct PairLossBPR {        // MACR_LOSS_BPR: -log(sig(p - n)), no epsilon                       macr_mf/model.py:264-275
+    __device__ static __forceinline__ float term(float p, float n, float invB, float &dp, float &dn) {
+        const float s = sigmoid_acc(p - n);
+        const float g = dneglog_sig(s, 0.0f) * invB;
+        dp = g; dn = -g;
+        return -logf(s);
+    }
+};
+struct PairLossBPRLgcn {    // MACR_LOSS_BPR_LGCN: -log(1e-9 + sig(sig(p) - sig(n)))               LightGCN.py:398-413
+    __device__ static __forceinline__ float term(float p, float n, float invB, float &dp, float &dn) {
+        const float eps = 1e-9f;
+        const float sp = sigmoid_acc(p), sn = sigmoid_acc(n);
+        const float y = sigmoid_acc(sp - sn);
+        const float g = dneglog_sig(y, eps) * invB;
+        dp = g * (sp * (1.0f - sp)); dn = -g * (sn * (1.0f - sn));
+        return -logf(y + eps);
+    }
+};
+__host__ __device__ __forceinline__ bool is_pair_loss(int kind) {
+    return kind == MACR_LOSS_NORMALBCE || kind == MACR_LOSS_BPR || kind == MACR_LOSS_BPR_LGCN;
+}
+// PL = the policy of a per-pair kind (is_pair_loss(kind) must hold)
+#define MACR_DISPATCH_PAIR_LOSS(kind, ...)                                                    \
+    switch (kind) {                                                                           \
+        case MACR_LOSS_BPR:      { using PL = macr::PairLossBPR;     __VA_ARGS__; } break;    \
+        case MACR_LOSS_BPR_LGCN: { using PL = macr::PairLossBPRLgcn; __VA_ARGS__; } break;    \
+        default:                 { using PL = macr::PairLossBCE;     __VA_ARGS__; } break;    \
+    }
+
 // ---- Adam (shared by the dense pass of train_kernels.hip and the fused epilogue of spmm_kernels.hip) -------------
 struct StepScalars {
     float lr_t;          // lr * sqrt(1-beta2^t) / (1-beta1^t)   (TF 1.14 Adam)

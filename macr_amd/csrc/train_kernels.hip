@@ -222,7 +222,7 @@ __device__ __forceinline__ void finalize_losses(const LossArgs &L, int lane, dou
     if (lane == 0) {
         const double Bd = (double)L.B;
         float mf;
-        if (L.kind == MACR_LOSS_NORMALBCE) {
+        if (is_pair_loss(L.kind)) {                              // normalbce, bpr: the per-pair losses' sums
             mf = (float)(bce / Bd);
         } else {
             const float Lo = (float)(lo / (Bd * Bd)), Li = (float)(li / Bd), Lu = (float)(lu / Bd);
@@ -1272,13 +1272,13 @@ __global__ __launch_bounds__(256) void k_pair_bwd(
 }
 
 // ----------------------------------------------------------------------------
-// pair_normal: `normalbce` forward + backward in one pass (genuinely per pair).
-//   mf = mean(-log(sig(p)+1e-9) - log(1-sig(n)+1e-9))            macr_mf/model.py:277-287
-//   dp = f'(p)/B, dn = g'(n)/B;  deu=dp*ei+dn*ej, dei=dp*eu, dej=dn*eu (+coef*row)
+// pair_normal: a per-pair loss (PL: normalbce, bpr, LightGCN's bpr; common.hpp) forward + backward in one pass.
+//   mf = mean(PL::term(p, n)), e.g. normalbce: mean(-log(sig(p)+1e-9) - log(1-sig(n)+1e-9))   macr_mf/model.py:277-287
+//   dp, dn = d mf / d p, d n;  deu=dp*ei+dn*ej, dei=dp*eu, dej=dn*eu (+coef*row)
 // Algorithmic HBM bytes per triple: 3 rows read + 3 gradient rows written + 12 B indices
 // = 24*d+12.  One wave per triple, lane k owns element k.
 // ----------------------------------------------------------------------------
-template <int D>
+template <class PL, int D>
 __global__ __launch_bounds__(256) void k_pair_normal(
     int B, const int32_t *__restrict__ u, const int32_t *__restrict__ i, const int32_t *__restrict__ j,
     const float *__restrict__ Usrc, const float *__restrict__ Isrc,
@@ -1298,7 +1298,7 @@ __global__ __launch_bounds__(256) void k_pair_normal(
         adam_pow_out[1] = p2 * b2;
     }
     float sq = 0.f, bce = 0.f;
-    const float eps = 1e-9f, invB = 1.0f / (float)B;
+    const float invB = 1.0f / (float)B;
     for (int chunk = blockIdx.x; chunk * kChunkT < B; chunk += gridDim.x) {      // see pair_bwd: equal positives of a chunk are added once
 #pragma unroll 1
         for (int q = 0; q < kChunkT / 4; ++q) {
@@ -1317,9 +1317,9 @@ __global__ __launch_bounds__(256) void k_pair_normal(
                 if (reg_on_gathered) sq += eu[e] * eu[e] + ei[e] * ei[e] + ej[e] * ej[e];
             }
             const float p = wave_sum(pp), n = wave_sum(nn);
-            const float sp = sigmoid_acc(p), sn = sigmoid_acc(n);
-            if (lane == 0) bce += -logf(sp + eps) + -logf((1.0f - sn) + eps);
-            const float dp = dneglog_sig(sp, eps) * invB, dn = dneglog_1msig(sn, eps) * invB;
+            float dp, dn;
+            const float term = PL::term(p, n, invB, dp, dn);
+            if (lane == 0) bce += term;
             if (act && gU) {                                    // gU == NULL: forward only (loss-only pass)
 #pragma unroll
                 for (int e = 0; e < EPL; ++e) {
@@ -1371,9 +1371,9 @@ __global__ __launch_bounds__(256) void k_refs_init(int B, int n_users, const int
     }
 }
 
-// normalbce forward+backward, one LPR-lane group per triple, float4 per lane; see k_pair_normal for the arithmetic.
+// per-pair loss (PL) forward+backward, one LPR-lane group per triple, float4 per lane; see k_pair_normal for the arithmetic.
 // stage: [3][B][d] gradient rows of (user, positive, negative) in batch order.
-template <int LPR>
+template <class PL, int LPR>
 __global__ __launch_bounds__(256) void k_pair_normal_stage(
     int B, const int32_t *__restrict__ u, const int32_t *__restrict__ i, const int32_t *__restrict__ j,
     const float *__restrict__ Usrc, const float *__restrict__ Isrc, float *__restrict__ stage,
@@ -1389,7 +1389,7 @@ __global__ __launch_bounds__(256) void k_pair_normal_stage(
         adam_pow_out[1] = p2 * b2;
     }
     float sq = 0.f, bce = 0.f;
-    const float eps = 1e-9f, invB = 1.0f / (float)B;
+    const float invB = 1.0f / (float)B;
     for (long long base = (long long)blockIdx.x * RPB; base < B; base += (long long)gridDim.x * RPB) {
         const long long t = base + g.slot;
         if (t >= B) continue;
@@ -1399,9 +1399,9 @@ __global__ __launch_bounds__(256) void k_pair_normal_stage(
         const float4 ej = ld4(Isrc + (size_t)rj * d + 4 * g.sub);
         const float p = group_sum<LPR>(dot4(eu, ei)), n = group_sum<LPR>(dot4(eu, ej));
         if (reg_on_gathered) sq += dot4(eu, eu) + dot4(ei, ei) + dot4(ej, ej);
-        const float sp = sigmoid_acc(p), sn = sigmoid_acc(n);
-        if (g.sub == 0) bce += -logf(sp + eps) + -logf((1.0f - sn) + eps);
-        const float dp = dneglog_sig(sp, eps) * invB, dn = dneglog_1msig(sn, eps) * invB;
+        float dp, dn;
+        const float term = PL::term(p, n, invB, dp, dn);
+        if (g.sub == 0) bce += term;
         // place (may be NULL): where reference (role, t) stands in the list sorted by row -- its gradient row goes THERE,
         // so that a row's references are consecutive staging rows for whoever sums them
         const size_t o0 = place ? place[t] : (size_t)t, o1 = place ? place[(size_t)B + t] : (size_t)B + t;
@@ -1912,11 +1912,11 @@ static int launch_pair(int kind, int B, int d, int n_urows, int n_irows, const i
     BatchSort sort = batch_sort_args(ws, B, u, i, j);
     if (ws.staged || loss_only) sort.B = 0;
     sort.outflag = ws.fwd + 6 * (size_t)ws.Bp; sort.nneu = ws.nneu; sort.ncbx = ws.ncbx;      // neutralised columns of the (B,B) launch (pair_fwd flags them)
-    if (kind == MACR_LOSS_NORMALBCE && loss_only) {            // forward of the per-pair loss, nothing written but partials
+    if (is_pair_loss(kind) && loss_only) {                    // forward of the per-pair loss, nothing written but partials
         const int nb = (B + kChunkT - 1) / kChunkT < 1024 ? (B + kChunkT - 1) / kChunkT : 1024;
-        MACR_DISPATCH_D(d, (k_pair_normal<D><<<nb, 256, 0, st>>>(B, u, i, j, Usrc, Isrc, nullptr, nullptr, nullptr, nullptr,
-                                                                ws.part, coef, reg_on_gathered, adam_pow, nullptr,
-                                                                ws.scal, hp->lr, hp->beta1, hp->beta2, nullptr)));
+        MACR_DISPATCH_PAIR_LOSS(kind, MACR_DISPATCH_D(d, (k_pair_normal<PL, D><<<nb, 256, 0, st>>>(
+                                              B, u, i, j, Usrc, Isrc, nullptr, nullptr, nullptr, nullptr, ws.part, coef,
+                                              reg_on_gathered, adam_pow, nullptr, ws.scal, hp->lr, hp->beta1, hp->beta2, nullptr))));
         MACR_CHECK_LAUNCH("pair_normal", st);
         return MACR_OK;
     }
@@ -1934,20 +1934,20 @@ static int launch_pair(int kind, int B, int d, int n_urows, int n_irows, const i
         MACR_CHECK_LAUNCH("ref_place", st);
         *sv_sorted = nullptr;                                    // (the indexed pass finds the rows by position)
     }
-    if (kind == MACR_LOSS_NORMALBCE) {
+    if (is_pair_loss(kind)) {
         if (ws.staged) {
-            MACR_DISPATCH_LPR(d, (k_pair_normal_stage<LPR><<<ws.nblk_bwd, 256, 0, st>>>(
-                                     B, u, i, j, Usrc, Isrc, ws.stage, ws.part, coef, reg_on_gathered, adam_pow, adam_pow,
-                                     ws.scal, hp->lr, hp->beta1, hp->beta2, listed ? rs.free_val : nullptr)));
+            MACR_DISPATCH_PAIR_LOSS(kind, MACR_DISPATCH_LPR(d, (k_pair_normal_stage<PL, LPR><<<ws.nblk_bwd, 256, 0, st>>>(
+                                              B, u, i, j, Usrc, Isrc, ws.stage, ws.part, coef, reg_on_gathered, adam_pow,
+                                              adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, listed ? rs.free_val : nullptr))));
             MACR_CHECK_LAUNCH("pair_normal", st);
             if (listed) return launch_seg_index(B, d, n_urows, n_irows, rs, true, gU, gI, tU, tI, ws, st);
             return launch_ref_sort_reduce(B, d, n_urows, n_irows, u, i, j, gU, gI, tU, tI, ws, st, sv_sorted);
         }
         k_batch_sort<<<(B + kBucketSpan - 1) / kBucketSpan, 256, 0, st>>>(sort);
         MACR_CHECK_LAUNCH("batch_sort", st);
-        MACR_DISPATCH_D(d, (k_pair_normal<D><<<ws.nblk_bwd, 256, 0, st>>>(B, ws.us, ws.is, ws.js, Usrc, Isrc, gU, gI, tU, tI,
-                                                                      ws.part, coef, reg_on_gathered, adam_pow, adam_pow,
-                                                                      ws.scal, hp->lr, hp->beta1, hp->beta2, cnt_pos)));
+        MACR_DISPATCH_PAIR_LOSS(kind, MACR_DISPATCH_D(d, (k_pair_normal<PL, D><<<ws.nblk_bwd, 256, 0, st>>>(
+                                              B, ws.us, ws.is, ws.js, Usrc, Isrc, gU, gI, tU, tI, ws.part, coef, reg_on_gathered,
+                                              adam_pow, adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, cnt_pos))));
         MACR_CHECK_LAUNCH("pair_normal", st);
         return MACR_OK;
     }
@@ -2034,7 +2034,7 @@ static void mf_adam_args(AdamArgs &a, long long &nb, bool tables, int loss_kind,
         add_seg(a, Q, mQ, vQ, gQ, tQ, n_items, nb);
     }
     // w: both branch losses; w_user: rubibceboth only (its gradient is None elsewhere -> TF leaves it alone)
-    if (loss_kind != MACR_LOSS_NORMALBCE) add_seg(a, w, mw, vw, ws.gw, nullptr, 1, nb, kBranchSlots, 2 * d);
+    if (!is_pair_loss(loss_kind)) add_seg(a, w, mw, vw, ws.gw, nullptr, 1, nb, kBranchSlots, 2 * d);
     if (loss_kind == MACR_LOSS_RUBIBCEBOTH) add_seg(a, wu, mwu, vwu, ws.gw + d, nullptr, 1, nb, kBranchSlots, 2 * d);
 }
 }  // namespace macr
@@ -2073,19 +2073,19 @@ static int mf_train_step(int loss_kind, int B, int d, int n_users, int n_items, 
                          float *vwu, float *gP, float *gQ, int32_t *touchedP, int32_t *touchedQ,
                          float *adam_pow, const macr_hyper *hp, float *losses, int flags, const macr_lazy_adam *lz,
                          void *workspace, size_t workspace_bytes, void *stream) {
-    MACR_REQUIRE(loss_kind == MACR_LOSS_NORMALBCE || loss_kind == MACR_LOSS_RUBIBCEBOTH || loss_kind == MACR_LOSS_RUBIBCE,
-                 MACR_E_INVALID, "mf_train_step: loss_kind=%d", loss_kind);
+    MACR_REQUIRE(loss_kind == MACR_LOSS_NORMALBCE || loss_kind == MACR_LOSS_RUBIBCEBOTH || loss_kind == MACR_LOSS_RUBIBCE ||
+                     loss_kind == MACR_LOSS_BPR, MACR_E_INVALID, "mf_train_step: loss_kind=%d", loss_kind);
     MACR_REQUIRE(B > 0 && n_users > 0 && n_items > 0, MACR_E_INVALID, "mf_train_step: B=%d n_users=%d n_items=%d", B,
                  n_users, n_items);
     MACR_REQUIRE(dim_supported(d), MACR_E_UNSUPPORTED, "mf_train_step: d=%d not in {32,64,128,256}", d);
     MACR_REQUIRE(u && i && j && P && Q && mP && vP && mQ && vQ && gP && gQ && touchedP && touchedQ && adam_pow &&
                      losses && workspace, MACR_E_INVALID, "mf_train_step: null pointer");
-    MACR_REQUIRE(loss_kind == MACR_LOSS_NORMALBCE || (w && wu && mw && vw && mwu && vwu), MACR_E_INVALID,
+    MACR_REQUIRE(is_pair_loss(loss_kind) || (w && wu && mw && vw && mwu && vwu), MACR_E_INVALID,
                  "mf_train_step: rubibceboth needs w, wu and their Adam slots");
     MACR_REQUIRE((flags & ~(MACR_STEP_DEFER | MACR_STEP_PENDING)) == 0, MACR_E_INVALID, "mf_train_step: flags=%d", flags);
-    MACR_REQUIRE(!flags || loss_kind != MACR_LOSS_NORMALBCE, MACR_E_INVALID,
+    MACR_REQUIRE(!flags || !is_pair_loss(loss_kind), MACR_E_INVALID,
                  "mf_train_step: deferred mode exists for the (B,B) losses only (flags=%d)", flags);
-    MACR_REQUIRE(!lz || loss_kind != MACR_LOSS_NORMALBCE, MACR_E_UNSUPPORTED,
+    MACR_REQUIRE(!lz || !is_pair_loss(loss_kind), MACR_E_UNSUPPORTED,
                  "mf_train_step_lazy: the lazy pass rides in the (B,B) launch (rubibceboth, rubibce)");
     if (int e = validate_hyper(hp, "mf_train_step")) return e;
     if (lz) if (int e = validate_lazy(lz, true, true, "mf_train_step_lazy")) return e;
@@ -2096,7 +2096,7 @@ static int mf_train_step(int loss_kind, int B, int d, int n_users, int n_items, 
                  "mf_train_step: workspace must be 256-byte aligned");
     hipStream_t st = as_stream(stream);
     const float coef = hp->decay / (float)hp->batch_size_cfg;       // d reg / d row  (model.py:219-221)
-    const bool rubi = loss_kind != MACR_LOSS_NORMALBCE;          // the (B,B) losses: rubibceboth, rubibce
+    const bool rubi = !is_pair_loss(loss_kind);                  // the (B,B) losses: rubibceboth, rubibce
     LossArgs L;
     L.part = ws.part; L.n_part = rubi ? ws.nblk_pair : ws.nblk_bwd;
     L.part2 = nullptr; L.n_part2 = 0;
@@ -2473,12 +2473,12 @@ extern "C" int macr_lazy_rows(long long n, int d, const int32_t *rows, const flo
 
 extern "C" int macr_shard_forward(int loss_kind, int B, int d, const float *rows3, const float *w, const float *wu,
                                   void *workspace, size_t workspace_bytes, void *stream) {
-    MACR_REQUIRE(loss_kind == MACR_LOSS_RUBIBCEBOTH || loss_kind == MACR_LOSS_RUBIBCE || loss_kind == MACR_LOSS_NORMALBCE,
-                 MACR_E_INVALID, "shard_forward: loss_kind=%d", loss_kind);
+    MACR_REQUIRE(loss_kind == MACR_LOSS_RUBIBCEBOTH || loss_kind == MACR_LOSS_RUBIBCE || loss_kind == MACR_LOSS_NORMALBCE ||
+                     loss_kind == MACR_LOSS_BPR, MACR_E_INVALID, "shard_forward: loss_kind=%d", loss_kind);
     MACR_REQUIRE(rows3 && w && wu, MACR_E_INVALID, "shard_forward: null pointer");
     MACR_SHARD_COMMON("shard_forward");
     k_iota3<<<grid_for(B), 256, 0, st>>>(B, sw.iota);
-    if (loss_kind == MACR_LOSS_NORMALBCE) { MACR_CHECK_LAUNCH("iota", st); return MACR_OK; }   // (forward and backward are one kernel: macr_shard_backward)
+    if (is_pair_loss(loss_kind)) { MACR_CHECK_LAUNCH("iota", st); return MACR_OK; }   // (forward and backward are one kernel: macr_shard_backward)
     PendingAdam none = {};
     const int user_branch = loss_kind == MACR_LOSS_RUBIBCEBOTH;
     const float *Isrc = rows3 + (size_t)B * d;
@@ -2520,8 +2520,8 @@ extern "C" int macr_shard_bxb(int B, int d, int rank, int world, void **partials
 extern "C" int macr_shard_backward(int loss_kind, int B, int d, const float *rows3, const float *w, const float *wu,
                                    float *adam_pow, const macr_hyper *hp, float *losses, void **branch_grads,
                                    size_t *branch_bytes, void *workspace, size_t workspace_bytes, void *stream) {
-    MACR_REQUIRE(loss_kind == MACR_LOSS_RUBIBCEBOTH || loss_kind == MACR_LOSS_RUBIBCE || loss_kind == MACR_LOSS_NORMALBCE,
-                 MACR_E_INVALID, "shard_backward: loss_kind=%d", loss_kind);
+    MACR_REQUIRE(loss_kind == MACR_LOSS_RUBIBCEBOTH || loss_kind == MACR_LOSS_RUBIBCE || loss_kind == MACR_LOSS_NORMALBCE ||
+                     loss_kind == MACR_LOSS_BPR, MACR_E_INVALID, "shard_backward: loss_kind=%d", loss_kind);
     MACR_REQUIRE(rows3 && w && wu && adam_pow && losses, MACR_E_INVALID, "shard_backward: null pointer");
     if (int e = validate_hyper(hp, "shard_backward")) return e;
     MACR_SHARD_COMMON("shard_backward");
@@ -2532,12 +2532,12 @@ extern "C" int macr_shard_backward(int loss_kind, int B, int d, const float *row
     L.alpha = hp->alpha; L.beta = hp->beta; L.decay = hp->decay; L.losses = losses;
     const float coef = hp->decay / (float)hp->batch_size_cfg;
     const float *Isrc = rows3 + (size_t)B * d;
-    if (loss_kind == MACR_LOSS_NORMALBCE) {
-        // macr_mf/model.py:277-287: no (B,B) term, no branch vectors -- per-pair forward and backward in one kernel, gradient
-        // rows of the whole batch into the staging buffer (replicated work, a few MB), then the loss sums
-        MACR_DISPATCH_LPR(d, (k_pair_normal_stage<LPR><<<ws.nblk_bwd, 256, 0, st>>>(
+    if (is_pair_loss(loss_kind)) {
+        // macr_mf/model.py:277-287 / :264-275: no (B,B) term, no branch vectors -- per-pair forward and backward in one kernel,
+        // gradient rows of the whole batch into the staging buffer (replicated work, a few MB), then the loss sums
+        MACR_DISPATCH_PAIR_LOSS(loss_kind, MACR_DISPATCH_LPR(d, (k_pair_normal_stage<PL, LPR><<<ws.nblk_bwd, 256, 0, st>>>(
                                  B, sw.iota, sw.iota + B, sw.iota + 2 * (size_t)B, rows3, Isrc, ws.stage, ws.part, coef, 1, adam_pow,
-                                 adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2)));
+                                 adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2))));
         MACR_CHECK_LAUNCH("pair_normal", st);
         L.n_part = ws.nblk_bwd; L.lpart = nullptr; L.n_lpart = 0;
         k_finalize_losses<<<1, 64, 0, st>>>(L);
@@ -2709,7 +2709,7 @@ static int shard_apply(int loss_kind, int B, int d, int n_users_loc, int n_items
     if (n_users_loc) add_seg(a, P, mP, vP, gP, touchedP, n_users_loc, nb);
     if (n_items_loc) add_seg(a, Q, mQ, vQ, gQ, touchedQ, n_items_loc, nb);
     const int n_tab = a.n_seg;
-    if (loss_kind != MACR_LOSS_NORMALBCE) add_seg(a, w, mw, vw, ws.gw, nullptr, 1, nb, kBranchSlots, 2 * d);
+    if (!is_pair_loss(loss_kind)) add_seg(a, w, mw, vw, ws.gw, nullptr, 1, nb, kBranchSlots, 2 * d);
     if (loss_kind == MACR_LOSS_RUBIBCEBOTH) add_seg(a, wu, mwu, vwu, ws.gw + d, nullptr, 1, nb, kBranchSlots, 2 * d);
     LossArgs L; L.losses = nullptr;
     if (indexed)
@@ -2828,8 +2828,8 @@ extern "C" int macr_lgcn_train_step_t(int loss_kind, int B, int d, int n_users, 
                                     float *vT, float *mw, float *vw, float *mwu, float *vwu, float *adam_pow,
                                     const macr_hyper *hp, float *losses, int flags, void *workspace,
                                     size_t workspace_bytes, void *stream) {
-    MACR_REQUIRE(loss_kind == MACR_LOSS_NORMALBCE || loss_kind == MACR_LOSS_RUBIBCEBOTH, MACR_E_INVALID,
-                 "lgcn_train_step: loss_kind=%d", loss_kind);
+    MACR_REQUIRE(loss_kind == MACR_LOSS_NORMALBCE || loss_kind == MACR_LOSS_RUBIBCEBOTH || loss_kind == MACR_LOSS_BPR_LGCN,
+                 MACR_E_INVALID, "lgcn_train_step: loss_kind=%d", loss_kind);
     MACR_REQUIRE(B > 0 && n_users > 0 && n_items > 0 && n_layers >= 0, MACR_E_INVALID,
                  "lgcn_train_step: B=%d n_users=%d n_items=%d n_layers=%d", B, n_users, n_items, n_layers);
     MACR_REQUIRE(dim_supported(d), MACR_E_UNSUPPORTED, "lgcn_train_step: d=%d not in {32,64,128,256}", d);
@@ -2888,7 +2888,7 @@ extern "C" int macr_lgcn_train_step_t(int loss_kind, int B, int d, int n_users, 
             return e;
         MACR_DISPATCH_D(d, (k_reg_scatter<D><<<ws.pair.nblk_bwd, 256, 0, st>>>(B, n_users, u, i, j, T, nullptr, coef, ws.pair.part2)));
         MACR_CHECK_LAUNCH("reg_scatter", st);
-        L.n_part = loss_kind == MACR_LOSS_NORMALBCE
+        L.n_part = is_pair_loss(loss_kind)
                        ? ((B + kChunkT - 1) / kChunkT < 1024 ? (B + kChunkT - 1) / kChunkT : 1024) : ws.pair.nblk_pair;
         k_finalize_losses<<<1, 64, 0, st>>>(L);
         MACR_CHECK_LAUNCH("finalize_losses", st);
@@ -2909,7 +2909,7 @@ extern "C" int macr_lgcn_train_step_t(int loss_kind, int B, int d, int n_users, 
     a.lpr = d / 4; a.lpr_shift = d == 32 ? 3 : d == 64 ? 4 : d == 128 ? 5 : 6;
     a.b1 = hp->beta1; a.b2 = hp->beta2; a.eps = hp->adam_eps;
     long long nb = 0;
-    L.n_part = loss_kind == MACR_LOSS_NORMALBCE ? ws.pair.nblk_bwd : ws.pair.nblk_pair;
+    L.n_part = is_pair_loss(loss_kind) ? ws.pair.nblk_bwd : ws.pair.nblk_pair;
     if (sparse) {
         // backward through the propagation with the optimizer in the last layer's epilogue (spmm_kernels.hip AdamFuse):
         // gradient row + ego-row regulariser (LightGCN.py:525-528) -> Adam on T, no G, no separate pass over the table

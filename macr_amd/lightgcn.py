@@ -5,8 +5,9 @@ commands exercise:
     --alg_type lightgcn, --adj_type pre
     --loss bce     -> opt_bce / loss_bce / mf_loss_bce / emb_loss_bce / reg_loss_bce            (:180-186, :415-429)
     --loss bceboth -> opt_two_bce_both / loss_two_bce_both / ...                               (:196-201, :495-532)
+    --loss bpr     -> opt / loss / mf_loss / emb_loss / reg_loss  (the parser's default)       (:173-178, :398-413)
     --test normal  -> batch_ratings (:166);  --test rubiboth -> rubi_ratings_both (:509) + update_c (:554)
-ngcf / gcn / gcmc embeddings, bpr / bce1 / bce2 losses, node and message
+ngcf / gcn / gcmc embeddings, bce1 / bce2 losses, node and message
 dropout, pretrained restore are out of scope (NotImplementedError).
 """
 import ast
@@ -19,7 +20,10 @@ from .mf import Fetch, xavier_uniform
 
 
 class LightGCN(object):
-    _LOSS = {"bce": ("bce", ops.LOSS_NORMALBCE), "bceboth": ("two_bce_both", ops.LOSS_RUBIBCEBOTH)}
+    _LOSS = {"bce": ("bce", ops.LOSS_NORMALBCE), "bceboth": ("two_bce_both", ops.LOSS_RUBIBCEBOTH),
+             "bpr": ("", ops.LOSS_BPR_LGCN)}
+    # optimizers created the first time their loss trains (Adam slots and a workspace of three propagated tables each)
+    _ON_DEMAND = (ops.LOSS_BPR_LGCN,)
 
     def __init__(self, data_config, args, pretrain_data=None, device=None, seed=12345, weights=None):
         if pretrain_data is not None:
@@ -84,14 +88,16 @@ class LightGCN(object):
             adj_t = ops.CSR.from_scipy(at, device)
         hyper = ops.make_hyper(self.lr, self.decay, self.alpha, self.beta, self.batch_size)
         self._opt = {}
+        self._adj, self._adj_t, self._hyper = adj, adj_t, hyper
         for loss, (suffix, kind) in self._LOSS.items():
-            self._opt[kind] = ops.LGCNState(T, self.n_users, self.n_items, w, wu, adj, self.n_layers, hyper,
-                                            self.batch_size, adj_t=adj_t)
-            setattr(self, "opt_" + suffix, Fetch("opt_" + suffix, "opt", kind))
-            setattr(self, "loss_" + suffix, Fetch("loss_" + suffix, "loss", kind))
-            setattr(self, "mf_loss_" + suffix, Fetch("mf_loss_" + suffix, "mf_loss", kind))
-            setattr(self, "emb_loss_" + suffix, Fetch("emb_loss_" + suffix, "reg_loss", kind))
-            setattr(self, "reg_loss_" + suffix, Fetch("reg_loss_" + suffix, "zero", kind))   # tf.constant(0.) :427
+            if kind not in self._ON_DEMAND:
+                self._opt[kind] = ops.LGCNState(T, self.n_users, self.n_items, w, wu, adj, self.n_layers, hyper,
+                                                self.batch_size, adj_t=adj_t)
+            # opt_bce ... ; the BPR graph's plain opt, loss ... (:173-178); reg_loss is tf.constant(0.) (:427, :411)
+            for base, role in (("opt", "opt"), ("loss", "loss"), ("mf_loss", "mf_loss"), ("emb_loss", "reg_loss"),
+                               ("reg_loss", "zero")):
+                name = base + "_" + suffix if suffix else base
+                setattr(self, name, Fetch(name, role, kind))
         st0 = self._opt[ops.LOSS_NORMALBCE]
         for st in self._opt.values():
             st.T, st.w, st.wu = st0.T, st0.w, st0.wu
@@ -99,7 +105,7 @@ class LightGCN(object):
         self.weights = {'user_embedding': self.T[:self.n_users], 'item_embedding': self.T[self.n_users:]}
         self.batch_ratings = Fetch("batch_ratings", "ratings", ops.SCORE_NORMAL)
         self.rubi_ratings_both = Fetch("rubi_ratings_both", "ratings", ops.SCORE_RUBI_BOTH)
-        for name in ("opt", "opt_two_bce1", "opt_two_bce2", "rubi_ratings1", "rubi_ratings2",
+        for name in ("opt_two_bce1", "opt_two_bce2", "rubi_ratings1", "rubi_ratings2",
                      "batch_ratings_causal_c"):
             setattr(self, name, Fetch(name, "unsupported"))
 
@@ -114,8 +120,16 @@ class LightGCN(object):
 
     def kind_of(self, loss):
         if loss not in self._LOSS:
-            raise NotImplementedError("--loss %s is not on the MI355X hot path (bce | bceboth)" % loss)
+            raise NotImplementedError("--loss %s is not on the MI355X hot path (bpr | bce | bceboth)" % loss)
         return self._LOSS[loss][1]
+
+    def _state(self, kind):
+        """the optimizer of loss `kind`, created on first use for the _ON_DEMAND kinds (sharing T, w, w_user)"""
+        st = self._opt.get(kind)
+        if st is None:
+            st = self._opt[kind] = ops.LGCNState(self.T, self.n_users, self.n_items, self.w, self.w_user, self._adj,
+                                                 self.n_layers, self._hyper, self.batch_size, adj_t=self._adj_t)
+        return st
 
     def to_device_batch(self, users, pos_items, neg_items):
         arr = np.asarray([users, pos_items, neg_items], dtype=np.int32)
@@ -129,10 +143,10 @@ class LightGCN(object):
         if not loss_only:
             for st in self._opt.values():
                 st._E = None
-        return self._opt[kind].step(kind, batch[0], batch[1], batch[2], losses, loss_only=loss_only)
+        return self._state(kind).step(kind, batch[0], batch[1], batch[2], losses, loss_only=loss_only)
 
     def opt_state(self, kind):
-        return self._opt[kind]
+        return self._state(kind)
 
     def propagated(self):
         """(ua_embeddings, ia_embeddings) = split(mean(E0, A E0, A^2 E0 ...))  (:288-309); computed once
@@ -160,8 +174,16 @@ class LightGCN(object):
 
     def load_state_dict(self, sd):
         self.T.copy_(sd["T"]); self.w.copy_(sd["w"]); self.w_user.copy_(sd["w_user"]); self.rubi_c = float(sd["rubi_c"])
+        for kind in self._ON_DEMAND:                            # a checkpoint of a run that trained it carries its optimizer
+            if "opt%d.adam_pow" % kind in sd:
+                self._state(kind)
         for kind, st in self._opt.items():
             st._E = None
+            if kind in self._ON_DEMAND and "opt%d.adam_pow" % kind not in sd:     # (saved before it first trained): fresh
+                for name in ("mT", "vT", "mw", "vw", "mwu", "vwu"):
+                    getattr(st, name).zero_()
+                st.adam_pow.copy_(torch.tensor([st.hyper.beta1, st.hyper.beta2]))
+                continue
             for name in ("mT", "vT", "mw", "vw", "mwu", "vwu", "adam_pow"):
                 getattr(st, name).copy_(sd["opt%d.%s" % (kind, name)])
 

@@ -5,6 +5,7 @@ exercise:
     --train normalbce   -> opt_bce / loss_bce / mf_loss_bce / reg_loss_bce           (:92-95, :277-287)
     --train rubibceboth -> opt_two_bce_both / loss_two_bce_both / ...                (:71-74, :185-222)
     --train rubibce     -> opt_two_bce / loss_two_bce / ...  (item branch only)      (:67-69, :158-183)
+    --train normal      -> opt / loss / mf_loss / reg_loss  (BPR)                     (:49-57, :264-275)
     --test  normal      -> batch_ratings                                             (:45)
     --test  rubi        -> rubi_ratings_both (rubibceboth) | rubi_ratings (other losses) + update_c   (:199, :141, :313)
     direct_minus_ratings(_both) (:142, :201) are served too (test(model_type="direct_minus_c"))
@@ -14,7 +15,7 @@ handles and `Session.run` dispatches them to the C-ABI kernels, so a caller
 written against the reference keeps working.  The fast path (`train_step`,
 `Evaluator`) avoids the per-step host synchronisation `sess.run` implies.
 
-Everything else in model.py (bpr / rubi / userc losses, BIASMF,
+Everything else in model.py (rubi / userc losses, BIASMF,
 IPS_BPRMF, CausalE) is out of scope and raises NotImplementedError.
 """
 import math
@@ -47,7 +48,10 @@ def xavier_uniform(shape, generator, device):
 
 class BPRMF(object):
     _TRAIN = {"normalbce": ("bce", ops.LOSS_NORMALBCE), "rubibceboth": ("two_bce_both", ops.LOSS_RUBIBCEBOTH),
-              "rubibce": ("two_bce", ops.LOSS_RUBIBCE)}
+              "rubibce": ("two_bce", ops.LOSS_RUBIBCE), "normal": ("", ops.LOSS_BPR)}
+    # optimizers created the first time their loss trains (their Adam slots and gradient scratch are table-sized: a run that
+    # never trains BPR allocates nothing for it)
+    _ON_DEMAND = (ops.LOSS_BPR,)
 
     def __init__(self, args, data_config, device=None, seed=12345, weights=None):
         self.n_users = data_config['n_users']
@@ -74,12 +78,12 @@ class BPRMF(object):
         # one optimizer instance (own Adam slots and step count) per `minimize` call of the reference
         self._opt = {}
         for train, (suffix, kind) in self._TRAIN.items():
-            self._opt[kind] = ops.MFState(self.weights['user_embedding'], self.weights['item_embedding'],
-                                          self.w, self.w_user, hyper, self.batch_size)
-            setattr(self, "opt_" + suffix, Fetch("opt_" + suffix, "opt", kind))
-            setattr(self, "loss_" + suffix, Fetch("loss_" + suffix, "loss", kind))
-            setattr(self, "mf_loss_" + suffix, Fetch("mf_loss_" + suffix, "mf_loss", kind))
-            setattr(self, "reg_loss_" + suffix, Fetch("reg_loss_" + suffix, "reg_loss", kind))
+            if kind not in self._ON_DEMAND:
+                self._opt[kind] = ops.MFState(self.weights['user_embedding'], self.weights['item_embedding'],
+                                              self.w, self.w_user, hyper, self.batch_size)
+            for role in ("opt", "loss", "mf_loss", "reg_loss"):        # opt_bce ... ; the BPR graph's plain opt, loss ... (:49-57)
+                name = role + "_" + suffix if suffix else role
+                setattr(self, name, Fetch(name, role, kind))
         # the MFState objects must all alias the same parameter storage
         st0 = self._opt[ops.LOSS_NORMALBCE]
         for st in self._opt.values():
@@ -92,7 +96,7 @@ class BPRMF(object):
         self.rubi_ratings = Fetch("rubi_ratings", "ratings", ops.SCORE_RUBI)                               # :141
         self.direct_minus_ratings = Fetch("direct_minus_ratings", "ratings", ops.SCORE_DIRECT_MINUS)      # :142
         self.direct_minus_ratings_both = Fetch("direct_minus_ratings_both", "ratings", ops.SCORE_DIRECT_MINUS_BOTH)   # :201
-        for name in ("opt", "opt_two", "opt2", "opt2_bce", "opt3", "opt3_bce", "opt_userc_bce",
+        for name in ("opt_two", "opt2", "opt2_bce", "opt3", "opt3_bce", "opt_userc_bce",
                      "user_const_ratings", "item_const_ratings", "user_rand_ratings", "item_rand_ratings",
                      "rubi_ratings_userc", "rubi_ratings_both_poptest"):
             setattr(self, name, Fetch(name, "unsupported"))
@@ -131,8 +135,16 @@ class BPRMF(object):
     # ------------------------------------------------------------------ fast path
     def kind_of(self, train):
         if train not in self._TRAIN:
-            raise NotImplementedError("--train %s is not on the MI355X hot path (normalbce | rubibce | rubibceboth)" % train)
+            raise NotImplementedError("--train %s is not on the MI355X hot path (normal | normalbce | rubibce | rubibceboth)" % train)
         return self._TRAIN[train][1]
+
+    def _state(self, kind):
+        """the optimizer of loss `kind`, created on first use for the _ON_DEMAND kinds (sharing the parameter storage)"""
+        st = self._opt.get(kind)
+        if st is None:
+            st0 = self._opt[ops.LOSS_NORMALBCE]
+            st = self._opt[kind] = ops.MFState(st0._P, st0._Q, st0.w, st0.wu, st0.hyper, self.batch_size)
+        return st
 
     def to_device_batch(self, users, pos_items, neg_items):
         """Python lists (what Data.sample returns) -> one (3,B) int32 device tensor."""
@@ -149,7 +161,7 @@ class BPRMF(object):
         for k, st in self._opt.items():
             if k != kind:
                 st.flush()
-        return self._opt[kind].step(kind, batch[0], batch[1], batch[2], losses, defer=defer)
+        return self._state(kind).step(kind, batch[0], batch[1], batch[2], losses, defer=defer)
 
     def sync(self):
         """Complete any pending parameter update (stream-ordered; no host synchronisation)."""
@@ -157,7 +169,7 @@ class BPRMF(object):
             st.flush()
 
     def opt_state(self, kind):
-        return self._opt[kind]
+        return self._state(kind)
 
     @property
     def user_embedding(self):
@@ -195,6 +207,9 @@ class BPRMF(object):
         self.sync()
         self.user_embedding.copy_(sd["user_embedding"]); self.item_embedding.copy_(sd["item_embedding"])
         self.w.copy_(sd["w"]); self.w_user.copy_(sd["w_user"]); self.rubi_c = float(sd["rubi_c"])
+        for kind in self._ON_DEMAND:                            # a checkpoint of a run that trained it carries its optimizer
+            if "opt%d.adam_pow" % kind in sd:
+                self._state(kind)
         for kind, st in self._opt.items():
             fresh = "opt%d.adam_pow" % kind not in sd          # (a row-sharded run's checkpoint carries ITS optimizer only)
             for name in ("mP", "vP", "mQ", "vQ", "mw", "vw", "mwu", "vwu"):
@@ -239,7 +254,7 @@ class ShardedBPRMF(object):
 
     def kind_of(self, train):
         if train not in self._TRAIN:
-            raise NotImplementedError("--train %s is not on the MI355X hot path (normalbce | rubibce | rubibceboth)" % train)
+            raise NotImplementedError("--train %s is not on the MI355X hot path (normal | normalbce | rubibce | rubibceboth)" % train)
         return self._TRAIN[train][1]
 
     def _model(self, kind):
@@ -278,7 +293,7 @@ class ShardedBPRMF(object):
         m = self._model(kind)
         counts = None
         hb = getattr(batch, "_macr_host_batch", None)        # set by to_device_batch on THIS tensor object only
-        if hb is not None and hb.shape == tuple(batch.shape) and self.world > 1 and m.split and kind != ops.LOSS_NORMALBCE:
+        if hb is not None and hb.shape == tuple(batch.shape) and self.world > 1 and m.split and not ops.is_pair_loss(kind):
             counts = m.route_counts_host(hb[0], hb[1], hb[2])
         out = m.step(batch[0], batch[1], batch[2], counts=counts)
         if losses is not None:

@@ -10,9 +10,9 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (LOSS_NORMALBCE, LOSS_RUBIBCEBOTH, LOSS_RUBIBCE, SCORE_NORMAL, SCORE_RUBI_BOTH, SCORE_RUBI,  # noqa: F401
+from ._lib import (LOSS_NORMALBCE, LOSS_RUBIBCEBOTH, LOSS_RUBIBCE, LOSS_BPR, LOSS_BPR_LGCN, SCORE_NORMAL, SCORE_RUBI_BOTH, SCORE_RUBI,  # noqa: F401
                    SCORE_DIRECT_MINUS, SCORE_DIRECT_MINUS_BOTH, MAX_TOPK,
-                   Hyper, MacrError, check)
+                   Hyper, MacrError, check, is_pair_loss)
 
 
 def _stream(device_index=None):
@@ -664,7 +664,7 @@ class MFState(object):
             self.flush()
         self.reserve(B)
         out = self.losses if losses is None else losses
-        defer = bool(defer) and kind != LOSS_NORMALBCE          # the (B,B) losses hide the Adam pass under their (B,B) kernel
+        defer = bool(defer) and not is_pair_loss(kind)          # the (B,B) losses hide the Adam pass under their (B,B) kernel
         if self.pending_B and kind != self.pending_kind:
             self.flush()
         flags = (_lib.STEP_DEFER if defer else 0) | (_lib.STEP_PENDING if self.pending_B else 0)

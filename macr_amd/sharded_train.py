@@ -27,7 +27,7 @@ import torch
 import torch.distributed as dist
 
 from . import sharding
-
+from ._lib import is_pair_loss
 
 def row_range(n_rows, rank, world):
     """Contiguous, balanced [lo, hi) of the rows rank owns (same rule as the evaluator's item shards)."""
@@ -161,8 +161,8 @@ class HipBackend(object):
         B = rows3.shape[1]
         self._lib.check(L.macr_shard_forward(self.kind, B, self.d, o._ptr(rows3), o._ptr(shard.w), o._ptr(shard.wu),
                                              o._ptr(self.ws), self.ws.numel(), o._stream()))
-        if self.kind == self._lib.LOSS_NORMALBCE:
-            return None                                     # no (B,B) term (macr_mf/model.py:277-287): nothing to sum over the ranks
+        if self.ops.is_pair_loss(self.kind):
+            return None                                     # no (B,B) term (model.py:277-287, :264-275): nothing to sum over the ranks
         ptr, nbytes = ctypes.c_void_p(), ctypes.c_size_t()
         self._lib.check(L.macr_shard_bxb(B, self.d, rank, world, ctypes.byref(ptr), ctypes.byref(nbytes), o._ptr(self.ws),
                                          self.ws.numel(), o._stream()))
@@ -177,7 +177,7 @@ class HipBackend(object):
                                               ctypes.byref(ptr), ctypes.byref(nbytes), o._ptr(self.ws), self.ws.numel(),
                                               o._stream()))
         if not nbytes.value:
-            return self.losses, None                        # normalbce: no branch vectors
+            return self.losses, None                        # normalbce, bpr: no branch vectors
         return self.losses, self._view(ptr, nbytes)         # losses; branch-vector partial rows (broadcast from rank 0)
 
     # ---- the split step: forward / backward of this rank's slice of the batch (macr_shard_*_slice)
@@ -493,7 +493,7 @@ class RowShardedMF(object):
         With several ranks and a branch loss the step is the SPLIT one (step_split; MACR_SHARD_SPLIT=0: the replicated
         forward / backward around one all-reduce of the batch's rows, below); `counts`: see step_split."""
         be = self.backend
-        if (self.world > 1 and self.split and hasattr(be, "slice_of") and getattr(be, "kind", 1) != 0):   # (kind 0 = normalbce: no (B,B) term)
+        if (self.world > 1 and self.split and hasattr(be, "slice_of") and not is_pair_loss(getattr(be, "kind", 1))):   # (per-pair: no (B,B) term)
             return self.step_split(u, i, j, counts)
         rows3 = be.gather(self, u, i, j)
         self._all_reduce(rows3, "rows")                           # 1. the batch's rows, everywhere

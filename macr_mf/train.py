@@ -250,7 +250,7 @@ def main(sweep=False):
         elif args.test == "rubi":
             if main_rank:
                 print('Epoch %d' % epoch)
-            if kind == ops.LOSS_NORMALBCE:
+            if ops.is_pair_loss(kind):
                 raise NotImplementedError("--test rubi needs a branch loss (--train rubibceboth | rubibce)")
             c_values = np.linspace(args.start, args.end, args.step) if sweep else [args.c]
             best = (0, 0, 0, 0, 0.0)               # train.py:540-544: bests start at 0
