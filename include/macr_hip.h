@@ -44,12 +44,16 @@ extern "C" {
 /* loss kinds */
 #define MACR_LOSS_NORMALBCE   0  /* --train normalbce   macr_mf/model.py:277-287 ; --loss bce     LightGCN.py:415-429 */
 #define MACR_LOSS_RUBIBCEBOTH 1  /* --train rubibceboth macr_mf/model.py:185-222 ; --loss bceboth LightGCN.py:495-532 */
-#define MACR_LOSS_RUBIBCE     2  /* --train rubibce     macr_mf/model.py:158-183 : item branch only (MF only);
-                                    the rubibceboth graph with sigmoid(e_u.w_user) := 1, w_user untouched        */
+#define MACR_LOSS_RUBIBCE     2  /* --train rubibce     macr_mf/model.py:158-183 : item branch only;
+                                    the rubibceboth graph with sigmoid(e_u.w_user) := 1, w_user untouched;
+                                    LightGCN --loss bce1 LightGCN.py:432-461 (abi 16): the same on the propagated rows  */
 #define MACR_LOSS_BPR         3  /* --train normal      macr_mf/model.py:264-275 (abi 16; MF only): -mean(log(sigmoid(p - n))),
                                     no epsilon (margins below about -100 overflow fp32: loss +inf, gradient NaN, as in TF) */
 #define MACR_LOSS_BPR_LGCN    4  /* --loss bpr          LightGCN.py:398-413 (abi 16; LightGCN only):
                                     -mean(log(1e-9 + sigmoid(sigmoid(p) - sigmoid(n)))), emb_loss on the ego rows      */
+#define MACR_LOSS_RUBIBCE_EGO 5  /* --loss bce2          LightGCN.py:463-493 (abi 16; LightGCN only): RUBIBCE whose branch logits
+                                    read the EGO item rows e0_i.w, e0_j.w -- their gradient reaches those rows directly, not
+                                    through the propagation; every MF and shard entry point refuses it as it refuses BPR_LGCN */
 /* NORMALBCE, BPR and BPR_LGCN are the PER-PAIR kinds: no (B,B) term and no branch vectors (w, w_user untouched).  Every
  * entry point that takes NORMALBCE takes the per-pair kind of its model; every one that refuses NORMALBCE refuses them too,
  * with the same error code. */
@@ -375,8 +379,10 @@ int macr_lgcn_propagate(int N, int d, int n_layers, const int32_t *rowptr, const
 /* One LightGCN training step.  Replaces sess.run([opt_X, loss_X, mf_loss_X,
  * emb_loss_X, reg_loss_X]) of macr_lightgcn/LightGCN.py:598-607: propagation,
  * gathers on the propagated table (:145-150), loss (loss_kind NORMALBCE :415-429,
- * RUBIBCEBOTH :495-532 or BPR_LGCN :398-413) with the regulariser on the ego rows
- * (:525-527), dense gradients through the propagation, Adam (:186 / :201 / :178).
+ * RUBIBCEBOTH :495-532, BPR_LGCN :398-413, RUBIBCE :432-461 or RUBIBCE_EGO :463-493)
+ * with the regulariser on the ego rows (:525-527), dense gradients through the
+ * propagation, Adam (:186 / :201 / :178 / opt_two_bce1 / opt_two_bce2).  w moves for the
+ * branch kinds, w_user for RUBIBCEBOTH only; both pointers are required whatever the kind.
  *   T (dev) fp32[N*d] = [user_embedding ; item_embedding], updated in place
  *   mT,vT Adam slots;  workspace (dev) >= macr_lgcn_train_workspace_bytes(B,N,d,plan_host) bytes, ZERO-FILLED ONCE
  *          before its first use (the batch-row flags and the hub rows' arrival counters are zero
@@ -585,6 +591,16 @@ int macr_score_topk_prologue_prep(int score_kind, int U, int n_local, int d, int
                                   const float *items, const float *w_item, float *sig_i,
                                   const float *users_tab, const int32_t *user_ids, const float *w_user, float *sig_u,
                                   float c, const float *c_dev, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The same with the items' branch factors taken from another table (abi 16): sig_i[r] = sigmoid(item_branch[r] . w_item)
+ * (item_branch: fp32[n_local*d], the rows in the order of `items`), the copies from `items` -- LightGCN's rubi_ratings2
+ * (LightGCN.py:473), whose item branch reads the EGO item rows while the scores read the propagated ones.  Still one launch;
+ * item_branch == items is macr_score_topk_prologue_prep.  (macr_score_topk_prologue reads `items` for the branch factors only:
+ * give it the branch table there.) */
+int macr_score_topk_prologue_prep_branch(int score_kind, int U, int n_local, int d, int K, int seeded_first_round,
+                                         const float *items, const float *item_branch, const float *w_item, float *sig_i,
+                                         const float *users_tab, const int32_t *user_ids, const float *w_user, float *sig_u,
+                                         float c, const float *c_dev, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
  * The same ranking for SEVERAL values of c at once -- the c sweep of the tuners

@@ -1485,7 +1485,7 @@ __device__ __forceinline__ void bf16_prep_c_block(int blk, int U, int n_local, c
                                                   float *__restrict__ unorm, uint32_t *__restrict__ qmax_bits,
                                                   const float *__restrict__ w_item = nullptr, const float *__restrict__ w_user = nullptr,
                                                   float *__restrict__ sig_i_out = nullptr, float *__restrict__ sig_u_out = nullptr,
-                                                  float *__restrict__ qpart = nullptr) {
+                                                  float *__restrict__ qpart = nullptr, const float *__restrict__ item_branch = nullptr) {
     constexpr int LPRB = D / 8, RPB = 256 / LPRB, RU = HALF ? D / 8 + 1 : StreamCfgC<D>::RU;
     __shared__ float s_max[4];
     const int n_pad = ((n_local + kTileItems - 1) / kTileItems) * kTileItems;
@@ -1506,7 +1506,10 @@ __device__ __forceinline__ void bf16_prep_c_block(int blk, int U, int n_local, c
         if (FUSED) {
             const float *wv = is_item ? w_item : w_user;      // (uniform over the row's lanes; w_user == NULL: one-branch scores)
             float pa = 0.f, pb = 0.f;
-            if (wv && (is_item || is_user)) { pa = dot4(a[t], ld4(wv + 8 * sub)); pb = dot4(b[t], ld4(wv + 8 * sub + 4)); }
+            // item_branch (rubi_ratings2): the items' factors from the row of another table, the same arithmetic
+            const float *bsrc = (is_item && item_branch) ? item_branch + (size_t)row[t] * D : nullptr;
+            const float4 ba = bsrc ? ld4(bsrc + 8 * sub) : a[t], bb = bsrc ? ld4(bsrc + 8 * sub + 4) : b[t];
+            if (wv && (is_item || is_user)) { pa = dot4(ba, ld4(wv + 8 * sub)); pb = dot4(bb, ld4(wv + 8 * sub + 4)); }
 #pragma unroll
             for (int m = LPRB >> 1; m >= 1; m >>= 1) { pa += __shfl_xor(pa, m, kWave); pb += __shfl_xor(pb, m, kWave); }
             sg_row = sigmoid_acc(pa + pb);
@@ -3728,7 +3731,8 @@ __global__ __launch_bounds__(256) void k_eval_prologue_prep(int n_prep, int U, i
                                                             uint4 *__restrict__ users_c, uint4 *__restrict__ items_c,
                                                             float *__restrict__ unorm, float *__restrict__ qpart,
                                                             uint32_t *__restrict__ base, size_t n_zero, size_t n_tau,
-                                                            uint32_t tau_bits, int set_tau, size_t n_max) {
+                                                            uint32_t tau_bits, int set_tau, size_t n_max,
+                                                            const float *__restrict__ item_branch) {
     if ((int)blockIdx.x >= n_prep) {
         const size_t blk = blockIdx.x - n_prep, nblk = gridDim.x - n_prep;
         const size_t total = n_zero + n_tau + n_max;
@@ -3741,7 +3745,7 @@ __global__ __launch_bounds__(256) void k_eval_prologue_prep(int n_prep, int U, i
     }
     bf16_prep_c_block<D, KIND, kPrepTripsAlone, true, true>(blockIdx.x, U, n_local, users_tab, user_ids, items, nullptr, nullptr,
                                                             c_dev ? *c_dev : c_val, users_c, items_c, unorm, nullptr,
-                                                            w_item, w_user, sig_i, sig_u, qpart);
+                                                            w_item, w_user, sig_i, sig_u, qpart, item_branch);
 }
 
 // ----------------------------------------------------------------------------
@@ -4716,17 +4720,19 @@ extern "C" int macr_score_topk_prologue(int filter, int U, int n_local, int d, i
 
 // The same plus the fp16 filter's operand copies (abi 15): one launch reads every row once.  The ranking call that follows takes
 // MACR_EVAL_WS_READY | MACR_EVAL_PREP_READY with MACR_EVAL_FILTER_F16 and the same score_kind, c, tables.
-extern "C" int macr_score_topk_prologue_prep(int score_kind, int U, int n_local, int d, int K, int seeded_first_round,
-                                             const float *items, const float *w_item, float *sig_i,
-                                             const float *users_tab, const int32_t *user_ids, const float *w_user, float *sig_u,
-                                             float c, const float *c_dev, void *workspace, size_t workspace_bytes, void *stream) {
+extern "C" int macr_score_topk_prologue_prep_branch(int score_kind, int U, int n_local, int d, int K, int seeded_first_round,
+                                                    const float *items, const float *item_branch, const float *w_item, float *sig_i,
+                                                    const float *users_tab, const int32_t *user_ids, const float *w_user,
+                                                    float *sig_u, float c, const float *c_dev, void *workspace,
+                                                    size_t workspace_bytes, void *stream) {
     hipStream_t st = as_stream(stream);
     MACR_REQUIRE(score_kind_valid(score_kind), MACR_E_INVALID, "score_topk_prologue_prep: score_kind=%d", score_kind);
     MACR_REQUIRE(U > 0 && n_local > 0, MACR_E_INVALID, "score_topk_prologue_prep: U=%d n_local=%d", U, n_local);
     MACR_REQUIRE(dim_supported(d), MACR_E_UNSUPPORTED, "score_topk_prologue_prep: d=%d not in {32,64,128,256}", d);
     MACR_REQUIRE(K >= 1 && K <= MACR_MAX_TOPK_FUSED, MACR_E_UNSUPPORTED, "score_topk_prologue_prep: K=%d outside [1,%d] (the fused ranking)", K,
                  MACR_MAX_TOPK_FUSED);
-    MACR_REQUIRE(items && w_item && sig_i && users_tab, MACR_E_INVALID, "score_topk_prologue_prep: null pointer (items, w_item, sig_i, users_tab)");
+    MACR_REQUIRE(items && item_branch && w_item && sig_i && users_tab, MACR_E_INVALID,
+                 "score_topk_prologue_prep: null pointer (items, item_branch, w_item, sig_i, users_tab)");
     MACR_REQUIRE((sig_u == nullptr) == (w_user == nullptr), MACR_E_INVALID, "score_topk_prologue_prep: sig_u and w_user come together");
     MACR_REQUIRE(!score_uses_sig_u(score_kind) || sig_u, MACR_E_INVALID, "score_topk_prologue_prep: score_kind %d needs sig_u / w_user", score_kind);
     MACR_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0, MACR_E_INVALID,
@@ -4742,10 +4748,18 @@ extern "C" int macr_score_topk_prologue_prep(int score_kind, int U, int n_local,
         k_eval_prologue_prep<D, KIND><<<n_prep + hp.grid, 256, 0, st>>>((int)n_prep, U, n_local, users_tab, user_ids, items, w_item, w_user, sig_i, sig_u,
                                                                        c, c_dev, ws.users_c, ws.items_c, ws.unorm, ws.qpart,
                                                                        static_cast<uint32_t *>(workspace), hp.n_zero, hp.n_tau, 0xff800000u,
-                                                                       hp.set_tau, hp.n_max);
+                                                                       hp.set_tau, hp.n_max, item_branch == items ? nullptr : item_branch);
     });
     MACR_CHECK_LAUNCH("eval_prologue_prep", st);
     return MACR_OK;
+}
+
+extern "C" int macr_score_topk_prologue_prep(int score_kind, int U, int n_local, int d, int K, int seeded_first_round,
+                                             const float *items, const float *w_item, float *sig_i,
+                                             const float *users_tab, const int32_t *user_ids, const float *w_user, float *sig_u,
+                                             float c, const float *c_dev, void *workspace, size_t workspace_bytes, void *stream) {
+    return macr_score_topk_prologue_prep_branch(score_kind, U, n_local, d, K, seeded_first_round, items, items, w_item, sig_i, users_tab, user_ids, w_user, sig_u, c, c_dev, workspace,
+                                                workspace_bytes, stream);
 }
 
 /* ---- c sweep -------------------------------------------------------------------------------------------------- */

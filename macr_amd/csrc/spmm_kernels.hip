@@ -111,6 +111,8 @@ struct AdamFuse {
     float b1, b2, eps, coef;      // coef = decay / batch_size
     float *dE;                    // gradient buffer of the pair kernels (rows of the batch are zeroed)
     double *emb_acc;              // [2048] partial sums of cnt * |T row|^2 (emb_loss), slot = row % 2048
+    float *sb;                    // NULL, or (LightGCN --loss bce2) a scalar per row: the row's gradient also gets sb[r] * bw, and
+    const float *bw;              // sb[r] is zeroed -- the item branch on the EGO rows, which does not pass through the propagation
 };
 
 struct SpmmArgs {
@@ -290,7 +292,8 @@ template <int D, int R, bool FUSE>
 __device__ __forceinline__ void spmm_records(const int32_t *__restrict__ rec, const float *__restrict__ X, float *Y, const float *S_in,
                                              float *S_out, float scale, int32_t *sp_rows, float *fT, float *fm, float *fv,
                                              const StepScalars *__restrict__ fscal, float *fdE, double *femb, float b1, float b2,
-                                             float eps, float coef, int w_trace = 0) {
+                                             float eps, float coef, int w_trace = 0, float *fsb = nullptr,
+                                             const float *__restrict__ fbw = nullptr) {
     static_assert(D == 64, "records: one column per lane");
 #ifdef MACR_SPMM_TRACE
     const unsigned long long tr_rt0 = __builtin_amdgcn_s_memrealtime(), tr_c0 = __builtin_readcyclecounter();
@@ -345,11 +348,15 @@ __device__ __forceinline__ void spmm_records(const int32_t *__restrict__ rec, co
             float th = th0[q], m = m0[q], vv = v0[q], sq = 0.f;
             float g = (s[q] + acc) * scale;
             if (cr) { g = fmaf(coef * (float)cr, th, g); sq = th * th; fdE[o] = 0.f; }
+            if (cr && fsb) g = fmaf(fsb[row[q]], fbw[lane], g);  // (wave-uniform) --loss bce2: the ego row's item branch
             adam1(th, m, vv, g, fscal->lr_t, b1, b2, eps);
             fT[o] = th; fm[o] = m; fv[o] = vv;
             if (cr) {
                 sq = wave_sum(sq);
-                if (lane == 0) { atomicAdd(femb + (row[q] & 2047), (double)cr * (double)sq); sp_rows[row[q]] = 0; }
+                if (lane == 0) {
+                    atomicAdd(femb + (row[q] & 2047), (double)cr * (double)sq); sp_rows[row[q]] = 0;
+                    if (fsb) fsb[row[q]] = 0.f;
+                }
             }
         } else {
             if (Y) Y[o] = acc;
@@ -387,7 +394,7 @@ __global__ __launch_bounds__(256) void k_spmm_row(const SpmmScalars P, const int
                                                   const int32_t *__restrict__ sp_u, const int32_t *__restrict__ sp_i,
                                                   const int32_t *__restrict__ sp_j, float *fT, float *fm, float *fv,
                                                   const StepScalars *__restrict__ fscal, float *fdE, double *femb,
-                                                  const int32_t *__restrict__ records) {
+                                                  const int32_t *__restrict__ records, float *fsb, const float *__restrict__ fbw) {
     struct {                       // (the names the body uses)
         int N, n_items, n_slots, n_groups; float scale;
         const int32_t *rowptr; const int4 *items;
@@ -439,7 +446,7 @@ __global__ __launch_bounds__(256) void k_spmm_row(const SpmmScalars P, const int
         if (P.n_single > 0 && w >= P.n_single) {                 // (wave-uniform) a record of short rows
             const int k = w - P.n_single;
             const int32_t *rec = records + (size_t)k * kRecInts;
-#define MACR_REC_ARGS rec, X, Y, S_in, S_out, P.scale, sp_cnt, fT, fm, fv, fscal, fdE, femb, P.b1, P.b2, P.eps, P.coef, w
+#define MACR_REC_ARGS rec, X, Y, S_in, S_out, P.scale, sp_cnt, fT, fm, fv, fscal, fdE, femb, P.b1, P.b2, P.eps, P.coef, w, fsb, fbw
             if (k < P.n_rec8) spmm_records<D, 8, FUSE>(MACR_REC_ARGS);
             else if (k < P.n_rec8 + P.n_rec4) spmm_records<D, 4, FUSE>(MACR_REC_ARGS);
             else if (k < P.n_rec8 + P.n_rec4 + P.n_rec2) spmm_records<D, 2, FUSE>(MACR_REC_ARGS);
@@ -619,6 +626,7 @@ __global__ __launch_bounds__(256) void k_spmm_row(const SpmmScalars P, const int
         }
         const int c = __builtin_amdgcn_readfirstlane(c0);       // references of the batch to this row (wave-uniform)
         const float lr_t = fscal->lr_t;
+        const float sb = (c && fsb) ? fsb[r] : 0.f;             // --loss bce2: the ego row's item branch (see AdamFuse)
         float sq = 0.f;
         if (writer) {
 #pragma unroll
@@ -627,6 +635,7 @@ __global__ __launch_bounds__(256) void k_spmm_row(const SpmmScalars P, const int
                 float th = th0[v], m = m0[v], vv = v0[v];
                 float g = (s[v] + acc[v]) * A.scale;
                 if (c) { g = fmaf(P.coef * (float)c, th, g); sq = fmaf(th, th, sq); fdE[o] = 0.f; }
+                if (c && fsb) g = fmaf(sb, fbw[colofs + 64 * v], g);
                 adam1(th, m, vv, g, lr_t, P.b1, P.b2, P.eps);
                 fT[o] = th; fm[o] = m; fv[o] = vv;
             }
@@ -636,6 +645,7 @@ __global__ __launch_bounds__(256) void k_spmm_row(const SpmmScalars P, const int
             if (lane == 0) {
                 atomicAdd(femb + (r & 2047), (double)c * (double)sq);
                 A.sp.rows[r] = 0;
+                if (fsb) fsb[r] = 0.f;
             }
         }
         return;
@@ -1025,7 +1035,7 @@ int launch_propagate(int N, int d, int n_layers, const int32_t *rowptr, const in
         // (the fused layer stays with the row kernel: there the optimizer's operands travel with the row's first gathers,
         // in the stream kernel they would be a dependent trip per row end -- measured 67 against 62 us)
         static const bool stream_fused = getenv("MACR_SPMM_STREAM_FUSED") && atoi(getenv("MACR_SPMM_STREAM_FUSED")) != 0;
-        if (have_stream && mode == kDense && (!fused || stream_fused) && sh.magic == kStreamMagic && (a.S_in == a.X || a.S_in == a.X + nd) &&
+        if (have_stream && mode == kDense && (!fused || (stream_fused && !af.sb)) && sh.magic == kStreamMagic && (a.S_in == a.X || a.S_in == a.X + nd) &&
             2 * nd * 4 < ((size_t)1 << 32)) {
             StreamArgs sa = {};
             sa.chunk_desc = sv.chunk_desc; sa.empties = sv.empties; sa.pcw = sv.pcw;
@@ -1063,7 +1073,7 @@ int launch_propagate(int N, int d, int n_layers, const int32_t *rowptr, const in
                                 af.b1, af.b2, af.eps, af.coef, rec ? ph.n_single : 0, ph.n_rec[0], ph.n_rec[1], ph.n_rec[2], ph.n_rec[3]};
 #define MACR_SPMM_ARGS ps, a.rowptr, a.col, a.val, a.items, a.slot_group, a.group_slot0, a.group_split, a.split_group0, \
                        a.arrivals, a.X, a.Y, a.S_in, a.S_out, a.slab, a.sp.cnt, a.sp.u, a.sp.i, a.sp.j, af.T, af.m, af.v,  \
-                       af.scal, af.dE, af.emb_acc, records
+                       af.scal, af.dE, af.emb_acc, records, af.sb, af.bw
 #define MACR_SPMM_ROW(D_)                                                                                         \
     do {                                                                                                          \
         if (mode == kSparseOut) k_spmm_row<D_, kSparseOut, false><<<grid, 256, 0, st>>>(MACR_SPMM_ARGS);          \

@@ -226,7 +226,7 @@ __device__ __forceinline__ void finalize_losses(const LossArgs &L, int lane, dou
             mf = (float)(bce / Bd);
         } else {
             const float Lo = (float)(lo / (Bd * Bd)), Li = (float)(li / Bd), Lu = (float)(lu / Bd);
-            mf = L.kind == MACR_LOSS_RUBIBCE ? Lo + L.alpha * Li            // macr_mf/model.py:178
+            mf = (L.kind == MACR_LOSS_RUBIBCE || L.kind == MACR_LOSS_RUBIBCE_EGO) ? Lo + L.alpha * Li    // macr_mf/model.py:178
                                              : Lo + L.alpha * Li + L.beta * Lu;               // :217
         }
         float regularizer = (float)(0.5 * sq);                  // tf.nn.l2_loss x3  (:219)
@@ -542,7 +542,9 @@ __global__ __launch_bounds__(256) void k_pair_fwd(
     const float *__restrict__ Usrc, const float *__restrict__ Isrc,
     const float *__restrict__ w, const float *__restrict__ wu,
     float *__restrict__ fwd, float *__restrict__ part, int reg_on_gathered, float *__restrict__ gw, PendingAdam pa,
-    int user_branch) {
+    int user_branch, const float *__restrict__ Bsrc = nullptr) {
+    // Bsrc (MACR_LOSS_RUBIBCE_EGO, LightGCN --loss bce2): the item rows the branch logits si, sj read (the ego table),
+    // NULL: the scored rows themselves
     constexpr int d = 4 * LPR;
     __shared__ float red[48];
     __shared__ float s_lr[PENDING == 2 ? kLazyRing : 1];
@@ -607,8 +609,10 @@ __global__ __launch_bounds__(256) void k_pair_fwd(
         }
         const float p = group_sum<LPR>(dot4(eu, ei));
         const float n = group_sum<LPR>(dot4(eu, ej));
-        const float si = group_sum<LPR>(dot4(ei, w4));
-        const float sj = group_sum<LPR>(dot4(ej, w4));
+        const float4 bi = Bsrc ? ld4(Bsrc + (size_t)ri * d + 4 * g.sub) : ei;
+        const float4 bj = Bsrc ? ld4(Bsrc + (size_t)rj * d + 4 * g.sub) : ej;
+        const float si = group_sum<LPR>(dot4(bi, w4));
+        const float sj = group_sum<LPR>(dot4(bj, w4));
         const float su = group_sum<LPR>(dot4(eu, wu4));
         if (reg_on_gathered) sq = dot4(eu, eu) + dot4(ei, ei) + dot4(ej, ej);
         if (g.sub == 0) {
@@ -1076,10 +1080,11 @@ struct WaveRow {
 // thread k owns element k and adds every DISTINCT row once -- equal rows of the chunk are summed first, adjacent or
 // not (the batch arrives bucketed by the low byte of the positive item, batch_bucket_block, so the hottest item of a
 // batch costs (#chunks it spans) serialised atomics instead of (#references)).
-template <int D>
+template <int D, bool EGO = false>
 __device__ __forceinline__ void combine_positive_rows(const int *s_pos, const float (*s_gi)[D], float *gI,
-                                                      int32_t *cnt = nullptr) {
+                                                      int32_t *cnt = nullptr, const float *s_sb = nullptr, float *sbr = nullptr) {
     // cnt (LightGCN): cnt[row] += the row's references in this chunk, one atomic per DISTINCT row of the chunk
+    // EGO: sbr[row] += the row's branch scalars s_sb[slot] in this chunk, the same way (k_pair_bwd<D, true>)
     // thread = (element k, part): part p of NP handles the distinct rows whose FIRST slot L has L % NP == p
     constexpr int NP = D >= 256 ? 1 : 256 / D;
     const int k = threadIdx.x % D, part = threadIdx.x / D;
@@ -1093,13 +1098,14 @@ __device__ __forceinline__ void combine_positive_rows(const int *s_pos, const fl
 #pragma unroll
         for (int s0 = 0; s0 < L; ++s0) first = first && rows[s0] != rows[L];
         if (!first) continue;
-        float acc = s_gi[L][k];
+        float acc = s_gi[L][k], sb = EGO ? s_sb[L] : 0.f;
         int mult = 1;
 #pragma unroll
         for (int s2 = L + 1; s2 < kChunkT; ++s2)
-            if (rows[s2] == rows[L]) { acc += s_gi[s2][k]; ++mult; }
+            if (rows[s2] == rows[L]) { acc += s_gi[s2][k]; ++mult; if (EGO) sb += s_sb[s2]; }
         MACR_ATOMIC_ADD(gI + (size_t)rows[L] * D + k, acc);
         if (cnt && k == 0) atomicAdd(cnt + rows[L], mult);
+        if (EGO && k == 0) MACR_ATOMIC_ADD(sbr + rows[L], sb);
     }
 }
 
@@ -1113,7 +1119,10 @@ __device__ __forceinline__ void combine_positive_rows(const int *s_pos, const fl
 //   (a few partial rows instead of one: 32 blocks per slot add without queueing on one line)
 // One wave per triple (grid-strided); lane k owns element k of every row.
 // ----------------------------------------------------------------------------
-template <int D>
+// EGO (MACR_LOSS_RUBIBCE_EGO, LightGCN --loss bce2): the branch logits read the rows of Bsrc (the ego table) -- the branch
+// terms dsi*w, dsj*w leave the gradient rows of Isrc and go, one scalar per item row, to sbr[row] += dsi (dsj) (the caller
+// adds sbr[row]*w to the ego row's gradient); w's gradient is formed from the Bsrc rows
+template <int D, bool EGO = false>
 __global__ __launch_bounds__(256) void k_pair_bwd(
     int B, int Bp, int nrb, int ncb, const int32_t *__restrict__ perm, const int32_t *__restrict__ u,
     const int32_t *__restrict__ i, const int32_t *__restrict__ j, const float *__restrict__ Usrc,
@@ -1122,11 +1131,13 @@ __global__ __launch_bounds__(256) void k_pair_bwd(
     const float *__restrict__ rowpart, const float *__restrict__ colpart,
     float *gU, float *gI, int32_t *touchedU, int32_t *touchedI, float *__restrict__ wpart,
     float alpha, float beta, float coef, float *adam_pow, StepScalars *scal, float lr, float b1, float b2,
-    LossArgs L, int32_t *cnt_pos, LazyState *lazy = nullptr, int nneu = 0) {
+    LossArgs L, int32_t *cnt_pos, LazyState *lazy = nullptr, int nneu = 0, const float *__restrict__ Bsrc = nullptr,
+    float *sbr = nullptr) {
     constexpr int EPL = WaveRow<D>::EPL;
     __shared__ float s_w[4][2][D];
     __shared__ float s_gi[kChunkT][D];
     __shared__ int s_pos[kChunkT];
+    __shared__ float s_sb[EGO ? kChunkT : 1];
     const int nblk = gridDim.x - 1;
     if ((int)blockIdx.x == nblk) {
         // Step bookkeeping, by one wave of an extra block.  Every Adam pass of the PREVIOUS update has completed
@@ -1171,6 +1182,7 @@ __global__ __launch_bounds__(256) void k_pair_bwd(
         // wait, atomics": eight dependent trips per wave instead of two; exec-mask branches end basic blocks and the
         // compiler hoists no load over them.)
         float reu[SPW][EPL], rei[SPW][EPL], rej[SPW][EPL];
+        float rbi[EGO ? SPW : 1][EPL], rbj[EGO ? SPW : 1][EPL];
         int rru[SPW], rri[SPW], rrj[SPW];
 #pragma unroll
         for (int q = 0; q < SPW; ++q) {             // (slots behind the end of the batch hold index 0: row 0, loaded and ignored)
@@ -1179,6 +1191,7 @@ __global__ __launch_bounds__(256) void k_pair_bwd(
             for (int e = 0; e < EPL; ++e) {
                 const int k = act ? lane + 64 * e : 0;
                 reu[q][e] = Usrc[(size_t)rru[q] * D + k]; rei[q][e] = Isrc[(size_t)rri[q] * D + k]; rej[q][e] = Isrc[(size_t)rrj[q] * D + k];
+                if (EGO) { rbi[q][e] = Bsrc[(size_t)rri[q] * D + k]; rbj[q][e] = Bsrc[(size_t)rrj[q] * D + k]; }
             }
         }
         // column sums dp,dn and row sums da,db of the (B,B) term: lane (q = lane/16, kk = lane%16) adds partials
@@ -1241,22 +1254,24 @@ __global__ __launch_bounds__(256) void k_pair_bwd(
                     const int k = lane + 64 * e;
                     const float eu = reu[q][e], ei = rei[q][e], ej = rej[q][e];
                     const float gu = fmaf(coef, eu, fmaf(dsu, wuk[e], fmaf(dnq, ej, dpq * ei)));
-                    const float gi = fmaf(coef, ei, fmaf(dsi, wk[e], dpq * eu));
-                    const float gj = fmaf(coef, ej, fmaf(dsj, wk[e], dnq * eu));
+                    const float gi = EGO ? fmaf(coef, ei, dpq * eu) : fmaf(coef, ei, fmaf(dsi, wk[e], dpq * eu));
+                    const float gj = EGO ? fmaf(coef, ej, dnq * eu) : fmaf(coef, ej, fmaf(dsj, wk[e], dnq * eu));
                     MACR_ATOMIC_ADD(gU + (size_t)ru * D + k, gu);
                     MACR_ATOMIC_ADD(gI + (size_t)rj * D + k, gj);
                     s_gi[slot][k] = gi;                         // positive row: combined per chunk below
-                    aw[e] = fmaf(dsi, ei, fmaf(dsj, ej, aw[e]));
+                    if (EGO) aw[e] = fmaf(dsi, rbi[EGO ? q : 0][e], fmaf(dsj, rbj[EGO ? q : 0][e], aw[e]));
+                    else aw[e] = fmaf(dsi, ei, fmaf(dsj, ej, aw[e]));
                     awu[e] = fmaf(dsu, eu, awu[e]);
                 }
             }
             if (lane == 0) {
+                if (EGO) { s_sb[EGO ? slot : 0] = dsi; MACR_ATOMIC_ADD(sbr + rj, dsj); }
                 s_pos[slot] = ri;
                 if (touchedU) { touchedU[ru] = 1; touchedI[ri] = 1; touchedI[rj] = 1; }
             }
         }
         __syncthreads();
-        combine_positive_rows<D>(s_pos, s_gi, gI, cnt_pos);
+        combine_positive_rows<D, EGO>(s_pos, s_gi, gI, cnt_pos, s_sb, sbr);
         __syncthreads();
     }
     if (act) {
@@ -1419,7 +1434,9 @@ __global__ __launch_bounds__(256) void k_pair_normal_stage(
 }
 
 // rubibceboth backward; see k_pair_bwd for the arithmetic.  The last block does the step bookkeeping.
-template <int LPR>
+// EGO: see k_pair_bwd<D, true>; the branch scalars dsi, dsj are STAGED like the gradient rows -- sst[o1], sst[o2] -- and
+// summed per row in list order by k_seg_reduce (the determinism of the rows)
+template <int LPR, bool EGO = false>
 __global__ __launch_bounds__(256) void k_pair_bwd_stage(
     int B, int Bp, int nrb, int ncb, const int32_t *__restrict__ u, const int32_t *__restrict__ i,
     const int32_t *__restrict__ j, const float *__restrict__ Usrc, const float *__restrict__ Isrc,
@@ -1427,7 +1444,7 @@ __global__ __launch_bounds__(256) void k_pair_bwd_stage(
     const float *__restrict__ rowpart, const float *__restrict__ colpart, float *__restrict__ stage,
     float *__restrict__ wpart, float alpha, float beta, float coef, float *adam_pow, StepScalars *scal, float lr,
     float b1, float b2, LossArgs L, const uint32_t *__restrict__ place = nullptr, int Bnorm = 0, LazyState *lazy = nullptr,
-    int nneu = 0) {
+    int nneu = 0, const float *__restrict__ Bsrc = nullptr, float *__restrict__ sst = nullptr) {
     // Bnorm > 0: the launch covers a SLICE of a batch of Bnorm triples (row-sharded training, macr_shard_backward_slice): u/i/j,
     // fwd, rowpart and colpart arrive offset to the slice, B is its length, the means are taken over the whole batch
     constexpr int d = 4 * LPR, RPB = RowGroup<LPR>::kRowsPerBlock;
@@ -1473,9 +1490,17 @@ __global__ __launch_bounds__(256) void k_pair_bwd_stage(
         const size_t o0 = place ? place[t] : (size_t)t, o1 = place ? place[(size_t)B + t] : (size_t)B + t;
         const size_t o2 = place ? place[2 * (size_t)B + t] : 2 * (size_t)B + t;       // (see k_pair_normal_stage)
         st4(stage + o0 * d + 4 * g.sub, fma4(coef, eu, fma4(dsu, wu4, fma4(dn, ej, scale4(dp, ei)))));
-        st4(stage + o1 * d + 4 * g.sub, fma4(coef, ei, fma4(dsi, w4, scale4(dp, eu))));
-        st4(stage + o2 * d + 4 * g.sub, fma4(coef, ej, fma4(dsj, w4, scale4(dn, eu))));
-        aw = fma4(dsi, ei, fma4(dsj, ej, aw));
+        if (EGO) {
+            const float4 bi = ld4(Bsrc + (size_t)ri * d + 4 * g.sub), bj = ld4(Bsrc + (size_t)rj * d + 4 * g.sub);
+            st4(stage + o1 * d + 4 * g.sub, fma4(coef, ei, scale4(dp, eu)));
+            st4(stage + o2 * d + 4 * g.sub, fma4(coef, ej, scale4(dn, eu)));
+            if (g.sub == 0) { sst[o1] = dsi; sst[o2] = dsj; }
+            aw = fma4(dsi, bi, fma4(dsj, bj, aw));
+        } else {
+            st4(stage + o1 * d + 4 * g.sub, fma4(coef, ei, fma4(dsi, w4, scale4(dp, eu))));
+            st4(stage + o2 * d + 4 * g.sub, fma4(coef, ej, fma4(dsj, w4, scale4(dn, eu))));
+            aw = fma4(dsi, ei, fma4(dsj, ej, aw));
+        }
         awu = fma4(dsu, eu, awu);
     }
     s_w[0][threadIdx.x] = aw; s_w[1][threadIdx.x] = awu;
@@ -1494,10 +1519,13 @@ __global__ __launch_bounds__(256) void k_pair_bwd_stage(
 // reference of a row, or a multiple of CH -- sums the (at most CH) staging rows of its chunk in list order and
 // stores the row (whole run in one chunk: plain store; gP/gQ rows are zero between steps) or adds it atomically
 // (runs cut into several chunks).
+// sst / sbr (LightGCN --loss bce2): the item references' staged branch scalars sst[r] are summed per item row the same
+// way, into sbr[row]
 template <int LPR>
 __global__ __launch_bounds__(256) void k_seg_reduce(int n, int n_users, uint32_t key_end, const uint32_t *__restrict__ sk,
                                                     const uint32_t *__restrict__ sv, const float *__restrict__ stage,
-                                                    float *gU, float *gI, int32_t *tU, int32_t *tI) {
+                                                    float *gU, float *gI, int32_t *tU, int32_t *tI,
+                                                    const float *__restrict__ sst = nullptr, float *sbr = nullptr) {
     constexpr int d = 4 * LPR, RPB = RowGroup<LPR>::kRowsPerBlock, CH = LPR < 16 ? LPR : 16;
     RowGroup<LPR> g;
     const long long p = (long long)blockIdx.x * RPB + g.slot;
@@ -1537,6 +1565,14 @@ __global__ __launch_bounds__(256) void k_seg_reduce(int n, int n_users, uint32_t
             MACR_ATOMIC_ADD(dst + 2, acc.z); MACR_ATOMIC_ADD(dst + 3, acc.w);
         } else {
             st4(dst, acc);
+        }
+        if (sst && !is_user) {                     // (wave-uniform pointer) the branch scalars of the run, in list order
+            float sb = 0.f;
+            for (int k2 = 0; k2 < len; ++k2) sb += sst[__shfl(vs, gbase + k2, kWave)];
+            if (g.sub == 0) {
+                if (multi) MACR_ATOMIC_ADD(sbr + row, sb);
+                else sbr[row] = sb;
+            }
         }
         if (g.sub == 0 && key0 != prev && tU) (is_user ? tU : tI)[row] = 1;
     }
@@ -1701,6 +1737,8 @@ struct AdamFuse {                 // = spmm_kernels.hip: dense Adam on the ego t
     float b1, b2, eps, coef;
     float *dE;
     double *emb_acc;
+    float *sb;
+    const float *bw;
 };
 int launch_propagate(int N, int d, int n_layers, const int32_t *rowptr, const int32_t *col, const float *val,
                      const void *plan_dev, const void *plan_host_header, const float *E0, float *E, float *work,
@@ -1710,6 +1748,20 @@ constexpr int kEmbSlots = 2048;
 
 // The tail of a fused LightGCN step: Adam on the branch vectors (their gradients are the partial rows pair_bwd left) and
 // the losses -- emb_loss from the sums of cnt * |T row|^2 the fused epilogue accumulated (cleared here for the next step).
+// dense layers, --loss bce2: the ego item rows' branch term G[r] += sbr[r] * w (LightGCN.py:463-493), sbr back to zero
+template <int LPR>
+__global__ __launch_bounds__(256) void k_ego_branch_rows(int n, const float *__restrict__ w, float *sbr, float *G) {
+    constexpr int d = 4 * LPR;
+    RowGroup<LPR> g;
+    const long long r = (long long)blockIdx.x * RowGroup<LPR>::kRowsPerBlock + g.slot;
+    if (r >= n) return;
+    const float s = sbr[r];
+    if (s == 0.f) return;
+    float *row = G + (size_t)r * d + 4 * g.sub;
+    st4(row, fma4(s, ld4(w + 4 * g.sub), ld4(row)));
+    if (g.sub == 0) sbr[r] = 0.f;
+}
+
 __global__ __launch_bounds__(256) void k_lgcn_finalize(AdamArgs a, const StepScalars *scal, LossArgs L, double *emb_acc) {
     __shared__ float4 s_red[256];
     if (blockIdx.x < a.n_seg) { adam_block<true>(a, a.seg[blockIdx.x].first_block, scal->lr_t, s_red); return; }
@@ -1884,7 +1936,8 @@ static int launch_seg_index(int B, int d, int n_urows, int n_irows, const RefSor
 }
 static int launch_ref_sort_reduce(int B, int d, int n_urows, int n_irows, const int32_t *u, const int32_t *i,
                                   const int32_t *j, float *gU, float *gI, int32_t *tU, int32_t *tI, const PairWs &ws,
-                                  hipStream_t st, const uint32_t **sv_sorted = nullptr) {
+                                  hipStream_t st, const uint32_t **sv_sorted = nullptr, const float *sst = nullptr,
+                                  float *sbr = nullptr) {
     const int n = 3 * B;
     const RefSort r = launch_ref_sort(B, n_urows, n_irows, u, i, j, ws, st);
     MACR_CHECK_LAUNCH("ref_sort", st);
@@ -1893,22 +1946,26 @@ static int launch_ref_sort_reduce(int B, int d, int n_urows, int n_irows, const 
         return launch_seg_index(B, d, n_urows, n_irows, r, false, gU, gI, tU, tI, ws, st);
     }
     MACR_DISPATCH_LPR(d, (k_seg_reduce<LPR><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
-                             n, n_urows, (uint32_t)(n_urows + n_irows), r.sk, r.sv, ws.stage, gU, gI, tU, tI)));
+                             n, n_urows, (uint32_t)(n_urows + n_irows), r.sk, r.sv, ws.stage, gU, gI, tU, tI, sst, sbr)));
     MACR_CHECK_LAUNCH("seg_reduce", st);
     return MACR_OK;
 }
 
 // forward + (B,B) + backward of the pair loss; on return (stream order) gU/gI hold the de-duplicated gradient rows.
 // n_urows / n_irows: rows of the tables Usrc / Isrc (sort key range).
+// Bsrc, sbr (MACR_LOSS_RUBIBCE_EGO): the item rows of the branch logits and the item rows' branch scalars (zero on entry;
+// sbr[row] = the sum of d mf_loss / d s over the row's references on return, in stream order)
 static int launch_pair(int kind, int B, int d, int n_urows, int n_irows, const int32_t *u, const int32_t *i,
                        const int32_t *j, const float *Usrc, const float *Isrc, const float *w, const float *wu,
                        float *gU, float *gI, int32_t *tU, int32_t *tI, float coef, int reg_on_gathered,
                        float *adam_pow, const macr_hyper *hp, const PairWs &ws, hipStream_t st,
                        const PendingAdam *pa = nullptr, const AdamArgs *pending = nullptr,
                        long long n_pending_blocks = 0, const LossArgs *finalize = nullptr, bool loss_only = false,
-                       int32_t *cnt_pos = nullptr, const uint32_t **sv_sorted = nullptr, LazyState *tick = nullptr) {
+                       int32_t *cnt_pos = nullptr, const uint32_t **sv_sorted = nullptr, LazyState *tick = nullptr,
+                       const float *Bsrc = nullptr, float *sbr = nullptr) {
     const int grid = ws.nblk_pair;
     const int user_branch = kind == MACR_LOSS_RUBIBCEBOTH;
+    const bool ego = Bsrc != nullptr;
     BatchSort sort = batch_sort_args(ws, B, u, i, j);
     if (ws.staged || loss_only) sort.B = 0;
     sort.outflag = ws.fwd + 6 * (size_t)ws.Bp; sort.nneu = ws.nneu; sort.ncbx = ws.ncbx;      // neutralised columns of the (B,B) launch (pair_fwd flags them)
@@ -1960,7 +2017,7 @@ static int launch_pair(int kind, int B, int d, int n_urows, int n_irows, const i
     } else {
         PendingAdam none = {};
         MACR_DISPATCH_LPR(d, (k_pair_fwd<LPR, 0><<<grid, 256, 0, st>>>(B, ws.Bp, u, i, j, Usrc, Isrc, w, wu, ws.fwd,
-                                                                      ws.part, reg_on_gathered, ws.gw, none, user_branch)));
+                                                                      ws.part, reg_on_gathered, ws.gw, none, user_branch, Bsrc)));
     }
     MACR_CHECK_LAUNCH("pair_fwd", st);
     switch (ws.rows) {
@@ -1972,6 +2029,18 @@ static int launch_pair(int kind, int B, int d, int n_urows, int n_irows, const i
     if (loss_only) return MACR_OK;
     LossArgs L;
     if (finalize) L = *finalize; else L.losses = nullptr;
+    if (ws.staged && ego) {
+        // the branch scalars are staged over the (B,B) row factors a, b of fwd (read by nothing after the (B,B) launch):
+        // sst[r] for the item references r in [B, 3B) is fwd[2 Bp + r - B]
+        MACR_REQUIRE(!listed, MACR_E_UNSUPPORTED, "pair: the ego branch has no indexed staging");
+        float *sst = ws.fwd + 2 * (size_t)ws.Bp - B;
+        MACR_DISPATCH_LPR(d, (k_pair_bwd_stage<LPR, true><<<ws.nblk_bwd + 1, 256, 0, st>>>(
+                                 B, ws.Bp, ws.nrb, ws.ncb, u, i, j, Usrc, Isrc, w, wu, ws.fwd, ws.rowpart, ws.colpart, ws.stage,
+                                 ws.gw, hp->alpha, hp->beta, coef, adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, L,
+                                 nullptr, 0, tick, ws.nneu, Bsrc, sst)));
+        MACR_CHECK_LAUNCH("pair_bwd", st);
+        return launch_ref_sort_reduce(B, d, n_urows, n_irows, u, i, j, gU, gI, tU, tI, ws, st, nullptr, sst, sbr);
+    }
     if (ws.staged) {
         MACR_DISPATCH_LPR(d, (k_pair_bwd_stage<LPR><<<ws.nblk_bwd + 1, 256, 0, st>>>(
                                  B, ws.Bp, ws.nrb, ws.ncb, u, i, j, Usrc, Isrc, w, wu, ws.fwd, ws.rowpart, ws.colpart, ws.stage,
@@ -1981,10 +2050,18 @@ static int launch_pair(int kind, int B, int d, int n_urows, int n_irows, const i
         if (listed) return launch_seg_index(B, d, n_urows, n_irows, rs, true, gU, gI, tU, tI, ws, st);
         return launch_ref_sort_reduce(B, d, n_urows, n_irows, u, i, j, gU, gI, tU, tI, ws, st, sv_sorted);
     }
-    MACR_DISPATCH_D(d, (k_pair_bwd<D><<<ws.nblk_bwd + 1, 256, 0, st>>>(B, ws.Bp, ws.nrb, ws.ncb, ws.perm, ws.us, ws.is, ws.js,
-                                                                      Usrc, Isrc, w, wu, ws.fwd, ws.rowpart, ws.colpart, gU,
-                                                                      gI, tU, tI, ws.gw, hp->alpha, hp->beta, coef, adam_pow,
-                                                                      ws.scal, hp->lr, hp->beta1, hp->beta2, L, cnt_pos, tick, ws.nneu)));
+    if (ego) {
+        MACR_DISPATCH_D(d, (k_pair_bwd<D, true><<<ws.nblk_bwd + 1, 256, 0, st>>>(B, ws.Bp, ws.nrb, ws.ncb, ws.perm, ws.us, ws.is, ws.js,
+                                                                            Usrc, Isrc, w, wu, ws.fwd, ws.rowpart, ws.colpart, gU,
+                                                                            gI, tU, tI, ws.gw, hp->alpha, hp->beta, coef, adam_pow,
+                                                                            ws.scal, hp->lr, hp->beta1, hp->beta2, L, cnt_pos, tick,
+                                                                            ws.nneu, Bsrc, sbr)));
+    } else {
+        MACR_DISPATCH_D(d, (k_pair_bwd<D><<<ws.nblk_bwd + 1, 256, 0, st>>>(B, ws.Bp, ws.nrb, ws.ncb, ws.perm, ws.us, ws.is, ws.js,
+                                                                          Usrc, Isrc, w, wu, ws.fwd, ws.rowpart, ws.colpart, gU,
+                                                                          gI, tU, tI, ws.gw, hp->alpha, hp->beta, coef, adam_pow,
+                                                                          ws.scal, hp->lr, hp->beta1, hp->beta2, L, cnt_pos, tick, ws.nneu)));
+    }
     MACR_CHECK_LAUNCH("pair_bwd", st);
     return MACR_OK;
 }
@@ -2782,7 +2859,7 @@ extern "C" int macr_lazy_flush(int d, long long n_rows_p, long long n_rows_q, fl
 // ---- LightGCN ---------------------------------------------------------------
 namespace macr {
 struct PlanHeaderLite { int32_t magic, n_items, n_split, n_slots, N, chunk, n_groups, reserved; };   // = spmm_kernels.hip PlanHeader
-struct LgcnWs { float *E, *dE, *G, *work; int32_t *cnt; double *emb_acc; PairWs pair; size_t bytes; };
+struct LgcnWs { float *E, *dE, *G, *work; int32_t *cnt; double *emb_acc; float *sbr; PairWs pair; size_t bytes; };
 static LgcnWs carve_lgcn_ws(void *base, int B, int N, int d, const PlanHeaderLite *ph, const PlanHeaderLite *pht = nullptr) {
     LgcnWs w;
     char *p = static_cast<char *>(base);
@@ -2798,6 +2875,7 @@ static LgcnWs carve_lgcn_ws(void *base, int B, int N, int d, const PlanHeaderLit
     w.work = static_cast<float *>(take(align_up((wf > wft ? wf : wft) * 4, 256)));
     w.cnt = static_cast<int32_t *>(take(align_up((size_t)N * 4, 256)));    // references of the current batch per row (zero between steps)
     w.emb_acc = static_cast<double *>(take(kEmbSlots * 8));                 // emb_loss partial sums (zero between steps)
+    w.sbr = static_cast<float *>(take(align_up((size_t)N * 4, 256)));      // --loss bce2: branch scalar per ego row (zero between steps)
     w.pair = carve_pair_ws(p ? p + off : nullptr, B, d);
     off += w.pair.bytes;
     w.bytes = off;
@@ -2828,7 +2906,8 @@ extern "C" int macr_lgcn_train_step_t(int loss_kind, int B, int d, int n_users, 
                                     float *vT, float *mw, float *vw, float *mwu, float *vwu, float *adam_pow,
                                     const macr_hyper *hp, float *losses, int flags, void *workspace,
                                     size_t workspace_bytes, void *stream) {
-    MACR_REQUIRE(loss_kind == MACR_LOSS_NORMALBCE || loss_kind == MACR_LOSS_RUBIBCEBOTH || loss_kind == MACR_LOSS_BPR_LGCN,
+    MACR_REQUIRE(loss_kind == MACR_LOSS_NORMALBCE || loss_kind == MACR_LOSS_RUBIBCEBOTH || loss_kind == MACR_LOSS_BPR_LGCN ||
+                     loss_kind == MACR_LOSS_RUBIBCE || loss_kind == MACR_LOSS_RUBIBCE_EGO,
                  MACR_E_INVALID, "lgcn_train_step: loss_kind=%d", loss_kind);
     MACR_REQUIRE(B > 0 && n_users > 0 && n_items > 0 && n_layers >= 0, MACR_E_INVALID,
                  "lgcn_train_step: B=%d n_users=%d n_items=%d n_layers=%d", B, n_users, n_items, n_layers);
@@ -2876,7 +2955,12 @@ extern "C" int macr_lgcn_train_step_t(int loss_kind, int B, int d, int n_users, 
     LossArgs L;
     L.part = ws.pair.part;
     L.part2 = ws.pair.part2; L.n_part2 = ws.pair.nblk_bwd;
-    L.lpart = ws.pair.lpart; L.n_lpart = loss_kind == MACR_LOSS_RUBIBCEBOTH ? ws.pair.nrb * ws.pair.ncbx : 0;
+    L.lpart = ws.pair.lpart; L.n_lpart = is_pair_loss(loss_kind) ? 0 : ws.pair.nrb * ws.pair.ncbx;
+    // --loss bce2 (LightGCN.py:463-493): the branch logits read the EGO item rows; their gradient reaches those rows directly,
+    // as one scalar per row (ws.sbr) times w, added where the ego-row regulariser enters (fused epilogue / G), not through dE
+    const bool ego = loss_kind == MACR_LOSS_RUBIBCE_EGO;
+    const float *Ti0 = ego ? T + (size_t)n_users * d : nullptr;
+    float *sbr_i = ego ? ws.sbr + n_users : nullptr;
     L.kind = loss_kind; L.B = B; L.batch_size_cfg = hp->batch_size_cfg;
     L.alpha = hp->alpha; L.beta = hp->beta; L.decay = hp->decay; L.losses = losses;
     const float coef = hp->decay / (float)hp->batch_size_cfg;
@@ -2884,7 +2968,8 @@ extern "C" int macr_lgcn_train_step_t(int loss_kind, int B, int d, int n_users, 
         // the reference's "test loss" pass (LightGCN.py:799-819): loss_X, mf_loss_X, emb_loss_X without opt_X
         float *Ei0 = ws.E + (size_t)n_users * d;
         if (int e = launch_pair(loss_kind, B, d, n_users, n_items, u, i, j, ws.E, Ei0, w, wu, nullptr, nullptr, nullptr,
-                                nullptr, 0.0f, 0, adam_pow, hp, ws.pair, st, nullptr, nullptr, 0, nullptr, true))
+                                nullptr, 0.0f, 0, adam_pow, hp, ws.pair, st, nullptr, nullptr, 0, nullptr, true, nullptr, nullptr,
+                                nullptr, Ti0, nullptr))
             return e;
         MACR_DISPATCH_D(d, (k_reg_scatter<D><<<ws.pair.nblk_bwd, 256, 0, st>>>(B, n_users, u, i, j, T, nullptr, coef, ws.pair.part2)));
         MACR_CHECK_LAUNCH("reg_scatter", st);
@@ -2902,7 +2987,7 @@ extern "C" int macr_lgcn_train_step_t(int loss_kind, int B, int d, int n_users, 
     float *Ei = ws.E + (size_t)n_users * d, *dEi = ws.dE + (size_t)n_users * d;
     if (int e = launch_pair(loss_kind, B, d, n_users, n_items, u, i, j, ws.E, Ei, w, wu, ws.dE, dEi, nullptr, nullptr,
                             0.0f, 0, adam_pow, hp, ws.pair, st, nullptr, nullptr, 0, nullptr, false,
-                            sparse && !ws.pair.staged ? ws.cnt + n_users : nullptr))
+                            sparse && !ws.pair.staged ? ws.cnt + n_users : nullptr, nullptr, nullptr, Ti0, sbr_i))
         return e;
     AdamArgs a;
     a.n_seg = 0;
@@ -2913,16 +2998,16 @@ extern "C" int macr_lgcn_train_step_t(int loss_kind, int B, int d, int n_users, 
     if (sparse) {
         // backward through the propagation with the optimizer in the last layer's epilogue (spmm_kernels.hip AdamFuse):
         // gradient row + ego-row regulariser (LightGCN.py:525-528) -> Adam on T, no G, no separate pass over the table
-        const AdamFuse fuse = {T, mT, vT, ws.pair.scal, hp->beta1, hp->beta2, hp->adam_eps, coef, ws.dE, ws.emb_acc};
+        const AdamFuse fuse = {T, mT, vT, ws.pair.scal, hp->beta1, hp->beta2, hp->adam_eps, coef, ws.dE, ws.emb_acc,
+                               ego ? ws.sbr : nullptr, w};
         SparseCtx spt = sp;
         spt.chunk = pht ? pht->chunk : 0x7fffffff;
         if (int e = launch_propagate(N, d, n_layers, rowptr_t, col_t, val_t, plan_t_dev, plan_t_host, ws.dE, ws.G, ws.work, st, &spt,
                                      kSparseIn, &fuse))
             return e;
-        if (loss_kind == MACR_LOSS_RUBIBCEBOTH) {
-            add_seg(a, w, mw, vw, ws.pair.gw, nullptr, 1, nb, kBranchSlots, 2 * d);
-            add_seg(a, wu, mwu, vwu, ws.pair.gw + d, nullptr, 1, nb, kBranchSlots, 2 * d);
-        }
+        // w: the branch losses; w_user: bceboth only (its gradient is None elsewhere -> TF leaves it alone)
+        if (!is_pair_loss(loss_kind)) add_seg(a, w, mw, vw, ws.pair.gw, nullptr, 1, nb, kBranchSlots, 2 * d);
+        if (loss_kind == MACR_LOSS_RUBIBCEBOTH) add_seg(a, wu, mwu, vwu, ws.pair.gw + d, nullptr, 1, nb, kBranchSlots, 2 * d);
         L.n_part2 = 0;                                  // emb_loss comes from ws.emb_acc
         k_lgcn_finalize<<<a.n_seg + 1, 256, 0, st>>>(a, ws.pair.scal, L, ws.emb_acc);
         MACR_CHECK_LAUNCH("lgcn_finalize", st);
@@ -2937,11 +3022,14 @@ extern "C" int macr_lgcn_train_step_t(int loss_kind, int B, int d, int n_users, 
     const int32_t *gu = ws.pair.staged ? u : ws.pair.us, *gi = ws.pair.staged ? i : ws.pair.is, *gj = ws.pair.staged ? j : ws.pair.js;
     MACR_DISPATCH_D(d, (k_reg_scatter<D><<<ws.pair.nblk_bwd, 256, 0, st>>>(B, n_users, gu, gi, gj, T, ws.G, coef, ws.pair.part2)));
     MACR_CHECK_LAUNCH("reg_scatter", st);
-    add_seg(a, T, mT, vT, ws.G, nullptr, N, nb);
-    if (loss_kind == MACR_LOSS_RUBIBCEBOTH) {
-        add_seg(a, w, mw, vw, ws.pair.gw, nullptr, 1, nb, kBranchSlots, 2 * d);
-        add_seg(a, wu, mwu, vwu, ws.pair.gw + d, nullptr, 1, nb, kBranchSlots, 2 * d);
+    if (ego) {
+        MACR_DISPATCH_LPR(d, (k_ego_branch_rows<LPR><<<(n_items + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
+                                 n_items, w, sbr_i, ws.G + (size_t)n_users * d)));
+        MACR_CHECK_LAUNCH("ego_branch_rows", st);
     }
+    add_seg(a, T, mT, vT, ws.G, nullptr, N, nb);
+    if (!is_pair_loss(loss_kind)) add_seg(a, w, mw, vw, ws.pair.gw, nullptr, 1, nb, kBranchSlots, 2 * d);
+    if (loss_kind == MACR_LOSS_RUBIBCEBOTH) add_seg(a, wu, mwu, vwu, ws.pair.gw + d, nullptr, 1, nb, kBranchSlots, 2 * d);
     k_adam_dense<false><<<(unsigned)nb, 256, 0, st>>>(a, ws.pair.scal, L);
     MACR_CHECK_LAUNCH("adam_dense", st);
     // (dE is zero again on return, as after a step with the sparse layers: their first backward layer may read all of it)

@@ -121,12 +121,14 @@ class Evaluator(object):
         return lo, hi, items_tab[lo:hi]
 
     # ------------------------------------------------------------------ ranking
-    def rank_local(self, kind, users_tab, user_ids, items_tab, K, w=None, wu=None, c=0.0):
+    def rank_local(self, kind, users_tab, user_ids, items_tab, K, w=None, wu=None, c=0.0, branch=None):
         """This rank's item shard: (val, idx) of shape (U,K) with GLOBAL item ids.
         users_tab/items_tab: full embedding tables (replicated on every rank); a rank scores only its contiguous
-        item shard."""
+        item shard.  branch (None: items_tab): the table, shaped and sharded like items_tab, the items' branch factors
+        sigmoid(row . w) come from (LightGCN's rubi_ratings2: the ego item rows)."""
         ws = sharding.world()[1]
         lo, hi, items_local = self._shard(items_tab)
+        branch_local = items_local if branch is None else self._shard(branch)[2]
         sig_u = sig_i = None
         U = self.n_queries
         both = kind in (ops.SCORE_RUBI_BOTH, ops.SCORE_DIRECT_MINUS_BOTH)
@@ -138,9 +140,9 @@ class Evaluator(object):
             pass
         elif both and items_local.shape[1] == users_tab.shape[1]:
             # sigmoid(e_i . w), sigmoid(e_u . w_user) (model.py:141-142,:199-201) in one launch
-            sig_i, sig_u = ops.branch_sigmoid2(items_local, w, None, users_tab, wu, user_ids)
+            sig_i, sig_u = ops.branch_sigmoid2(branch_local, w, None, users_tab, wu, user_ids)
         elif kind != ops.SCORE_NORMAL:
-            sig_i = ops.branch_sigmoid(items_local, w)              # sigmoid(e_i . w)      model.py:141-142,:199-201
+            sig_i = ops.branch_sigmoid(branch_local, w)             # sigmoid(e_i . w)      model.py:141-142,:199-201
             if both:
                 sig_u = ops.branch_sigmoid(users_tab, wu, user_ids)     # sigmoid(e_u . w_user) model.py:199,:201
         if U <= self.max_queries_per_pass:
@@ -152,10 +154,11 @@ class Evaluator(object):
             seeds = self.__dict__.setdefault("_seeds", {})
             use = (self.use_seeds and ws == 1 and K <= _lib_consts.MAX_TOPK_FUSED       # (the wide ranking takes no seeds)
                    and self._shape_uses_seeds(hi - lo, items_tab.shape[1]))
-            seed = seeds.get((K, lo, hi)) if use else None
+            skey = (K, lo, hi) + (() if branch is None else (branch.data_ptr(),))     # (rubi1 and rubi2 rank differently)
+            seed = seeds.get(skey) if use else None
             seeded = self._ranked_seeded = seed is not None and self._seeded_now
             if use and seed is None:
-                seed = seeds[(K, lo, hi)] = torch.full((U, ops.SEED_WIDTH), -1, dtype=torch.int32, device=self.device)
+                seed = seeds[skey] = torch.full((U, ops.SEED_WIDTH), -1, dtype=torch.int32, device=self.device)
             # the ranking leaves its best SEED_WIDTH candidates per query in `seed` (in place): the next ranking's seeds
             mask = self._mask_local if self._local_own is not None else self.mask
             mode = self._topk_mode
@@ -165,9 +168,11 @@ class Evaluator(object):
                          and self._shape_uses_seeds(hi - lo, items_tab.shape[1]))
             if fold_prep:
                 sig_i, sig_u = ops.score_topk_prologue_prep(kind, users_tab, user_ids, items_local, K, w, wu if both else None, c,
-                                                            seeded_first_round=seeded and mode == "first")
+                                                            seeded_first_round=seeded and mode == "first",
+                                                            item_branch=None if branch is None else branch_local)
             elif fold:
-                sig_i, sig_u = ops.score_topk_prologue(users_tab, user_ids, items_local, K, w, wu if both else None,
+                # (the prologue reads its item rows for the branch factors only: the branch table stands there)
+                sig_i, sig_u = ops.score_topk_prologue(users_tab, user_ids, branch_local, K, w, wu if both else None,
                                                        seeded_first_round=seeded and mode == "first", filter=self.filter_now)
             vals, idx = ops.score_topk(kind, users_tab, user_ids, items_local, K, sig_u, sig_i, c, mask, lo,
                                        seed=seed if seeded else None, seed_out=seed,
@@ -247,13 +252,14 @@ class Evaluator(object):
             cache[key] = bool(_lib.lib().macr_score_topk_uses_seeds(self.n_queries, n_local, d))
         return cache[key]
 
-    def _has_seeds(self, K, n_items):
+    def _has_seeds(self, K, n_items, branch=None):
+        bk = () if branch is None else (branch.data_ptr(),)
         if self._local_own is not None:
-            return (K, 0, self._local_own.n) in self.__dict__.get("_seeds", {})
+            return (K, 0, self._local_own.n) + bk in self.__dict__.get("_seeds", {})
         if self.local_items_range is not None:
-            return (K,) + tuple(self.local_items_range) in self.__dict__.get("_seeds", {})
+            return (K,) + tuple(self.local_items_range) + bk in self.__dict__.get("_seeds", {})
         rank, ws = sharding.world()
-        return (K,) + tuple(sharding.item_shard_range(n_items, rank, ws)) in self.__dict__.get("_seeds", {})
+        return (K,) + tuple(sharding.item_shard_range(n_items, rank, ws)) + bk in self.__dict__.get("_seeds", {})
 
     def _stats_readback(self, seeded):
         """after a ranking was launched: its stats travel to the host behind it (no synchronisation here)"""
@@ -263,12 +269,12 @@ class Evaluator(object):
             self._stats_evt = torch.cuda.Event()
             self._stats_evt.record()
 
-    def rank(self, kind, users_tab, user_ids, items_tab, K, w=None, wu=None, c=0.0, fill_masked=False):
+    def rank(self, kind, users_tab, user_ids, items_tab, K, w=None, wu=None, c=0.0, fill_masked=False, branch=None):
         """Top-K item ids for every query user: (val (U,K), idx (U,K), cnt (U,)); the shards' top-K are all-gathered
         (one collective) and merged."""
         self._seed_feedback()
         self._ranked_seeded = False
-        vals, idx = self.rank_local(kind, users_tab, user_ids, items_tab, K, w, wu, c)
+        vals, idx = self.rank_local(kind, users_tab, user_ids, items_tab, K, w, wu, c, branch)
         self._stats_readback(self._ranked_seeded)
         fill = self.mask if fill_masked else None
         if sharding.world()[1] == 1:
@@ -278,10 +284,10 @@ class Evaluator(object):
         return ops.topk_merge(gv, gi, fill)
 
     # ------------------------------------------------------------------ MF flavour
-    def test_mf(self, kind, users_tab, user_ids, items_tab, Ks, w=None, wu=None, c=0.0):
+    def test_mf(self, kind, users_tab, user_ids, items_tab, Ks, w=None, wu=None, c=0.0, branch=None):
         """-> {'precision','recall','ndcg','hit_ratio'}: np.ndarray(len(Ks)) float64, the mean over the
         query users (train.py:286-290 accumulates re[...]/n_test_users)."""
-        m = self._means("mf", kind, users_tab, user_ids, items_tab, tuple(Ks), w, wu, c).cpu().numpy()
+        m = self._means("mf", kind, users_tab, user_ids, items_tab, tuple(Ks), w, wu, c, branch).cpu().numpy()
         return {'precision': m[0].copy(), 'recall': m[1].copy(), 'ndcg': m[2].copy(), 'hit_ratio': m[3].copy()}
 
     def _finish(self, flavour, vals, idx, Ks, out=None):
@@ -310,8 +316,8 @@ class Evaluator(object):
         _, ix, _ = ops.topk_merge(vals, idx, self.mask)                                      # -inf fill, batch_test.py:124-134
         return ops.colmean(ops.metrics_foldout(ix, self.gt, hr_in_ap_slot=True), out=out)   # (U,5*max_top) fp32
 
-    def _direct(self, flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c):
-        vals, idx = self.rank_local(kind, users_tab, user_ids, items_tab, max(Ks), w, wu, c)
+    def _direct(self, flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, branch=None):
+        vals, idx = self.rank_local(kind, users_tab, user_ids, items_tab, max(Ks), w, wu, c, branch)
         if sharding.world()[1] > 1:
             lv, li, _ = ops.topk_merge(vals, idx)
             vals, idx = sharding.gather_topk(lv, li)
@@ -328,7 +334,7 @@ class Evaluator(object):
             self._c_host = float(c)
         return self._c_dev
 
-    def _means(self, flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c):
+    def _means(self, flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, branch=None):
         """The device part of an evaluation.  An evaluator ranks the same queries against the same (in-place updated)
         tables every epoch, and the ~14 launches of one evaluation are issued from Python between two host
         synchronisations: on one GPU the sequence is captured once into a HIP graph and replayed (one launch instead
@@ -340,26 +346,26 @@ class Evaluator(object):
         world = sharding.world()[1]
         if (self.optimistic and self.use_graph and world == 1 and self.device.type == "cuda"
                 and self.n_queries <= self.max_queries_per_pass and max(Ks) <= _lib_consts.MAX_TOPK_FUSED):
-            return self._means_optimistic(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c)
+            return self._means_optimistic(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, branch)
         self._last_info = None
         # (no seeds yet for this K and shard: the first ranking samples, and leaves them)
-        seeded = self._seed_feedback() and self.n_queries <= self.max_queries_per_pass and self._has_seeds(max(Ks), items_tab.shape[0])
+        seeded = self._seed_feedback() and self.n_queries <= self.max_queries_per_pass and self._has_seeds(max(Ks), items_tab.shape[0], branch)
         self._seeded_now = seeded        # the warm-up run of a capture creates the seeds: the capture itself must not pick them up
         try:
-            return self._means_launch(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, world, seeded)
+            return self._means_launch(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, world, seeded, branch=branch)
         finally:
             self._stats_readback(seeded)
 
-    def _means_optimistic(self, flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c):
+    def _means_optimistic(self, flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, branch=None):
         """First round only, results in pinned host memory; the rest of the ranking when the first round says so."""
         if self._stats_evt is not None:           # (a stats copy of the complete path still in flight: not needed any more)
             self._stats_evt = None
-        seeded = (self.use_seeds and self._seed_skip == 0 and self._has_seeds(max(Ks), items_tab.shape[0]))
+        seeded = (self.use_seeds and self._seed_skip == 0 and self._has_seeds(max(Ks), items_tab.shape[0], branch))
         if self.use_seeds and self._seed_skip > 0:
             self._seed_skip -= 1
         used = self.filter_now
         try:
-            return self._means_optimistic_run(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, seeded)
+            return self._means_optimistic_run(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, seeded, branch)
         finally:
             info = getattr(self, "_last_info", None) or {}
             if used == "f16":
@@ -382,11 +388,11 @@ class Evaluator(object):
             if getattr(self, "_last_info", None) is not None:
                 self._last_info["filter"] = used
 
-    def _means_optimistic_run(self, flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, seeded):
+    def _means_optimistic_run(self, flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, seeded, branch=None):
         self._seeded_now = seeded
         self._topk_mode = "first"
         try:
-            out = self._means_launch(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, 1, seeded, mode="first")
+            out = self._means_launch(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, 1, seeded, mode="first", branch=branch)
             first_entry = self._last_entry
         finally:
             self._topk_mode = None
@@ -415,7 +421,7 @@ class Evaluator(object):
             return out.clone()
         self._topk_mode, self._repair_bufs = "repair", first_entry[3]
         try:
-            out = self._means_launch(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, 1, seeded, mode="repair")
+            out = self._means_launch(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, 1, seeded, mode="repair", branch=branch)
         finally:
             self._topk_mode, self._repair_bufs = None, None
         torch.cuda.current_stream().synchronize()
@@ -431,10 +437,10 @@ class Evaluator(object):
         st = self._stats.tolist()
         return {"seeded": bool(self._last_seeded), "query_blocks_relisted": st[0], "exact_fallback": st[1], "redone": False}
 
-    def _means_launch(self, flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, world, seeded, mode=None):
+    def _means_launch(self, flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, world, seeded, mode=None, branch=None):
         self._last_entry = None
         if not self.use_graph:
-            return self._direct(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c)
+            return self._direct(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, branch)
         host_out = None
         if mode:
             hk = (flavour, Ks)
@@ -443,7 +449,7 @@ class Evaluator(object):
                 self._host_out[hk] = torch.zeros(shape, dtype=torch.float64).pin_memory()
             host_out = self._host_out[hk]
         key = (flavour, mode, self.filter_now, kind, seeded, users_tab.data_ptr(), None if user_ids is None else user_ids.data_ptr(), items_tab.data_ptr(),
-               Ks, None if w is None else w.data_ptr(), None if wu is None else wu.data_ptr(),
+               Ks, None if w is None else w.data_ptr(), None if wu is None else wu.data_ptr(), None if branch is None else branch.data_ptr(),
                torch.cuda.current_stream().cuda_stream, world)
         entry = self._graphs.get(key)
         if entry is None:
@@ -463,14 +469,14 @@ class Evaluator(object):
                     self._topk_mode = None        # (the complete sequence: its result needs no check)
                     self._stats_first.zero_()
                     self._complete_ran = True     # (its own statistics are in self._stats: _means_optimistic_run reads them)
-                return self._direct(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c)
-            self._direct(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c)     # warm-up: allocations, caches, attributes
+                return self._direct(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, branch)
+            self._direct(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, branch)     # warm-up: allocations, caches, attributes
             torch.cuda.synchronize()
             K = max(Ks)
             if world == 1:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    vals, idx = self.rank_local(kind, users_tab, user_ids, items_tab, K, w, wu, c)
+                    vals, idx = self.rank_local(kind, users_tab, user_ids, items_tab, K, w, wu, c, branch)
                     out = self._finish(flavour, vals, idx, Ks, out=host_out)
                 stages = (g, None, None, None)
                 # what a repair round must continue on: the first round's outputs AND the workspace it was captured with
@@ -481,7 +487,7 @@ class Evaluator(object):
                 # all-gather (RCCL), one graph from the gathered lists to the means
                 ga = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(ga):
-                    vals, idx = self.rank_local(kind, users_tab, user_ids, items_tab, K, w, wu, c)
+                    vals, idx = self.rank_local(kind, users_tab, user_ids, items_tab, K, w, wu, c, branch)
                     lv, li, _ = ops.topk_merge(vals, idx)
                 gv, gi = sharding.gather_topk(lv, li)                    # static inputs of the second graph
                 gb = torch.cuda.CUDAGraph()
@@ -491,7 +497,7 @@ class Evaluator(object):
                 first_bufs = None
             # the graphs bake in the addresses of everything they touched: keep the inputs and the cached scratch
             # (ranking workspace, mask bitmaps) alive for as long as they exist, whatever the caches do later
-            keep = [users_tab, user_ids, items_tab, w, wu, c, ops._topk_ws_cache.get(items_tab.device)]
+            keep = [users_tab, user_ids, items_tab, w, wu, c, branch, ops._topk_ws_cache.get(items_tab.device)]
             keep.extend(self.__dict__.get("_seeds", {}).values())
             local = [] if self._local_own is None else [self._mask_local] + list(self._mask_local.__dict__.get("_row_ranges", {}).values())
             for csr in [self.mask] + list(self.mask.__dict__.get("_row_ranges", {}).values()) + local:
@@ -507,14 +513,14 @@ class Evaluator(object):
         return out
 
     # ------------------------------------------------------------------ c sweep (tuners)
-    def _sweep_direct(self, flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c_dev):
-        sig_i = ops.branch_sigmoid(items_tab, w)
+    def _sweep_direct(self, flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c_dev, branch=None):
+        sig_i = ops.branch_sigmoid(items_tab if branch is None else branch, w)
         sig_u = ops.branch_sigmoid(users_tab, wu, user_ids) if kind in (ops.SCORE_RUBI_BOTH, ops.SCORE_DIRECT_MINUS_BOTH) else None
         vals, idx = ops.score_topk_sweep(kind, users_tab, user_ids, items_tab, max(Ks), sig_u, sig_i, c_dev, self.mask, 0,
                                          filter=self.filter)
         return torch.stack([self._finish(flavour, vals[g:g + 1], idx[g:g + 1], Ks) for g in range(c_dev.numel())])
 
-    def sweep_means(self, flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, cs):
+    def sweep_means(self, flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, cs, branch=None):
         """Column means of the per-user metrics for every c of `cs`, (len(cs), ...).  On one GPU the values go through
         the shared-listing-pass kernel in groups of up to four (one captured graph per group size, the group's values
         in a device array the kernels read at run time); item-sharded runs evaluate c by c."""
@@ -526,7 +532,7 @@ class Evaluator(object):
         one_by_one = os.environ.get("MACR_SWEEP_ONE_BY_ONE", "0") == "1"
         if (one_by_one or sharding.world()[1] > 1 or kind == ops.SCORE_NORMAL or self.n_queries > self.max_queries_per_pass
                 or max(Ks) > _lib.MAX_TOPK_FUSED):           # (the shared-listing-pass kernels rank K <= 32)
-            return torch.stack([self._means(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c).clone() for c in cs])
+            return torch.stack([self._means(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, branch).clone() for c in cs])
         outs = []
         for a in range(0, len(cs), _lib.MAX_SWEEP):
             chunk = cs[a:a + _lib.MAX_SWEEP]
@@ -537,34 +543,34 @@ class Evaluator(object):
             c_dev = bufs[n]
             c_dev.copy_(torch.tensor(chunk, dtype=torch.float32), non_blocking=False)
             if not self.use_graph:
-                outs.append(self._sweep_direct(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c_dev).clone())
+                outs.append(self._sweep_direct(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c_dev, branch).clone())
                 continue
             key = ("sweep", n, flavour, self.filter, kind, users_tab.data_ptr(), None if user_ids is None else user_ids.data_ptr(),
-                   items_tab.data_ptr(), Ks, w.data_ptr(), None if wu is None else wu.data_ptr(),
+                   items_tab.data_ptr(), Ks, w.data_ptr(), None if wu is None else wu.data_ptr(), None if branch is None else branch.data_ptr(),
                    torch.cuda.current_stream().cuda_stream)
             entry = self._graphs.get(key)
             if entry is None:
-                self._sweep_direct(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c_dev)       # warm-up
+                self._sweep_direct(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c_dev, branch)       # warm-up
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    out = self._sweep_direct(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c_dev)
-                keep = [users_tab, user_ids, items_tab, w, wu, c_dev, ops._sweep_ws_cache.get(items_tab.device)]
+                    out = self._sweep_direct(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c_dev, branch)
+                keep = [users_tab, user_ids, items_tab, w, wu, c_dev, branch, ops._sweep_ws_cache.get(items_tab.device)]
                 keep.extend(self.mask.__dict__.get("_mask_bits", {}).values())
                 entry = self._graphs[key] = ((g, None, None, None), out, keep)
             entry[0][0].replay()
             outs.append(entry[1].clone())
         return torch.cat(outs)
 
-    def test_mf_sweep(self, kind, users_tab, user_ids, items_tab, Ks, w, wu, cs):
+    def test_mf_sweep(self, kind, users_tab, user_ids, items_tab, Ks, w, wu, cs, branch=None):
         """test_mf for every c of `cs` -> list of result dicts (the c sweep of macr_mf/tune.py:545-578)."""
-        m = self.sweep_means("mf", kind, users_tab, user_ids, items_tab, tuple(Ks), w, wu, cs).cpu().numpy()
+        m = self.sweep_means("mf", kind, users_tab, user_ids, items_tab, tuple(Ks), w, wu, cs, branch).cpu().numpy()
         return [{'precision': x[0].copy(), 'recall': x[1].copy(), 'ndcg': x[2].copy(), 'hit_ratio': x[3].copy()} for x in m]
 
-    def test_lgcn_sweep(self, kind, users_tab, user_ids, items_tab, Ks, w, wu, cs):
+    def test_lgcn_sweep(self, kind, users_tab, user_ids, items_tab, Ks, w, wu, cs, branch=None):
         top_show = np.sort(np.asarray(Ks))
         max_top = int(top_show.max())
-        m = self.sweep_means("lgcn", kind, users_tab, user_ids, items_tab, tuple(Ks), w, wu, cs).cpu().numpy()
+        m = self.sweep_means("lgcn", kind, users_tab, user_ids, items_tab, tuple(Ks), w, wu, cs, branch).cpu().numpy()
         out = []
         for x in m:
             final = x.reshape(5, max_top)[:, top_show - 1]
@@ -572,12 +578,12 @@ class Evaluator(object):
         return out
 
     # ------------------------------------------------------------------ LightGCN flavour
-    def test_lgcn(self, kind, users_tab, user_ids, items_tab, Ks, w=None, wu=None, c=0.0):
+    def test_lgcn(self, kind, users_tab, user_ids, items_tab, Ks, w=None, wu=None, c=0.0, branch=None):
         """-> {'hr','recall','ndcg'}: np.ndarray(len(Ks)) (batch_test.py:134-161): C++-style fp32 prefix
         metrics, HR := 1[recall@k != 0], mean over users, columns Ks-1 in ascending-K order."""
         top_show = np.sort(np.asarray(Ks))
         max_top = int(top_show.max())
-        final = self._means("lgcn", kind, users_tab, user_ids, items_tab, tuple(Ks), w, wu, c).cpu().numpy()
+        final = self._means("lgcn", kind, users_tab, user_ids, items_tab, tuple(Ks), w, wu, c, branch).cpu().numpy()
         final = final.reshape(5, max_top)[:, top_show - 1]
         return {'hr': final[2].copy(), 'recall': final[1].copy(), 'ndcg': final[3].copy()}
 

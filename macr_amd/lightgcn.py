@@ -6,9 +6,14 @@ commands exercise:
     --loss bce     -> opt_bce / loss_bce / mf_loss_bce / emb_loss_bce / reg_loss_bce            (:180-186, :415-429)
     --loss bceboth -> opt_two_bce_both / loss_two_bce_both / ...                               (:196-201, :495-532)
     --loss bpr     -> opt / loss / mf_loss / emb_loss / reg_loss  (the parser's default)       (:173-178, :398-413)
+    --loss bce1    -> opt_two_bce1 / loss_two_bce1 / ...  item branch on the propagated rows   (:188-193, :432-461)
+    --loss bce2    -> opt_two_bce2 / loss_two_bce2 / ...  item branch on the ego rows          (:194-199, :463-493)
     --test normal  -> batch_ratings (:166);  --test rubiboth -> rubi_ratings_both (:509) + update_c (:554)
-ngcf / gcn / gcmc embeddings, bce1 / bce2 losses, node and message
+    --test rubi1 / rubi2 -> rubi_ratings1 (:442) / rubi_ratings2 (:473): (y - c) sigmoid(e_i . w), the branch on the
+                      propagated / the ego item rows
+ngcf / gcn / gcmc embeddings, batch_ratings_causal_c, node and message
 dropout, pretrained restore are out of scope (NotImplementedError).
+
 """
 import ast
 
@@ -21,9 +26,12 @@ from .mf import Fetch, xavier_uniform
 
 class LightGCN(object):
     _LOSS = {"bce": ("bce", ops.LOSS_NORMALBCE), "bceboth": ("two_bce_both", ops.LOSS_RUBIBCEBOTH),
-             "bpr": ("", ops.LOSS_BPR_LGCN)}
+             "bpr": ("", ops.LOSS_BPR_LGCN), "bce1": ("two_bce1", ops.LOSS_RUBIBCE),
+             "bce2": ("two_bce2", ops.LOSS_RUBIBCE_EGO)}
     # optimizers created the first time their loss trains (Adam slots and a workspace of three propagated tables each)
-    _ON_DEMAND = (ops.LOSS_BPR_LGCN,)
+    _ON_DEMAND = (ops.LOSS_BPR_LGCN, ops.LOSS_RUBIBCE, ops.LOSS_RUBIBCE_EGO)
+    # the kind of the rubi_ratings2 fetch: SCORE_RUBI with the item branch on the ego rows
+    RUBI_EGO = (ops.SCORE_RUBI, "ego")
 
     def __init__(self, data_config, args, pretrain_data=None, device=None, seed=12345, weights=None):
         if pretrain_data is not None:
@@ -105,9 +113,9 @@ class LightGCN(object):
         self.weights = {'user_embedding': self.T[:self.n_users], 'item_embedding': self.T[self.n_users:]}
         self.batch_ratings = Fetch("batch_ratings", "ratings", ops.SCORE_NORMAL)
         self.rubi_ratings_both = Fetch("rubi_ratings_both", "ratings", ops.SCORE_RUBI_BOTH)
-        for name in ("opt_two_bce1", "opt_two_bce2", "rubi_ratings1", "rubi_ratings2",
-                     "batch_ratings_causal_c"):
-            setattr(self, name, Fetch(name, "unsupported"))
+        self.rubi_ratings1 = Fetch("rubi_ratings1", "ratings", ops.SCORE_RUBI)
+        self.rubi_ratings2 = Fetch("rubi_ratings2", "ratings", self.RUBI_EGO)
+        self.batch_ratings_causal_c = Fetch("batch_ratings_causal_c", "unsupported")
 
     def create_model_str(self, args):
         log_dir = '/' + self.alg_type + '/layers_' + str(self.n_layers) + '/dim_' + str(self.emb_dim)
@@ -120,7 +128,7 @@ class LightGCN(object):
 
     def kind_of(self, loss):
         if loss not in self._LOSS:
-            raise NotImplementedError("--loss %s is not on the MI355X hot path (bpr | bce | bceboth)" % loss)
+            raise NotImplementedError("--loss %s is not on the MI355X hot path (bpr | bce | bceboth | bce1 | bce2)" % loss)
         return self._LOSS[loss][1]
 
     def _state(self, kind):
@@ -154,13 +162,19 @@ class LightGCN(object):
         E = self._opt[ops.LOSS_NORMALBCE].propagated()
         return E[:self.n_users], E[self.n_users:]
 
+    def ego_items(self):
+        """the ego item rows (item_embedding): the item branch of bce2 / rubi_ratings2 reads them (:466-470)"""
+        return self.T[self.n_users:]
+
     def ratings(self, kind, user_batch):
+        """kind: a score kind, or RUBI_EGO (rubi_ratings2: the branch factors from the ego item rows)"""
+        kind, ego = (kind[0], True) if kind == self.RUBI_EGO else (kind, False)
         uid = torch.as_tensor(list(user_batch), dtype=torch.int32, device=self.device)
         ua, ia = self.propagated()
         ia = ia.contiguous()
         sig_u = sig_i = None
         if kind != ops.SCORE_NORMAL:
-            sig_i = ops.branch_sigmoid(ia, self.w)
+            sig_i = ops.branch_sigmoid(self.ego_items() if ego else ia, self.w)
         if kind in (ops.SCORE_RUBI_BOTH, ops.SCORE_DIRECT_MINUS_BOTH):
             sig_u = ops.branch_sigmoid(ua, self.w_user, uid)
         return ops.score_matrix(kind, ua, uid, ia, sig_u, sig_i, self.rubi_c)

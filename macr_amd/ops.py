@@ -10,7 +10,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (LOSS_NORMALBCE, LOSS_RUBIBCEBOTH, LOSS_RUBIBCE, LOSS_BPR, LOSS_BPR_LGCN, SCORE_NORMAL, SCORE_RUBI_BOTH, SCORE_RUBI,  # noqa: F401
+from ._lib import (LOSS_NORMALBCE, LOSS_RUBIBCEBOTH, LOSS_RUBIBCE, LOSS_BPR, LOSS_BPR_LGCN, LOSS_RUBIBCE_EGO, SCORE_NORMAL, SCORE_RUBI_BOTH, SCORE_RUBI,  # noqa: F401
                    SCORE_DIRECT_MINUS, SCORE_DIRECT_MINUS_BOTH, MAX_TOPK,
                    Hyper, MacrError, check, is_pair_loss)
 
@@ -315,16 +315,26 @@ def score_topk_prologue(users_tab, user_ids, items, K, w_item, w_user=None, seed
     return sig_i, sig_u
 
 
-def score_topk_prologue_prep(kind, users_tab, user_ids, items, K, w_item, w_user=None, c=0.0, seeded_first_round=False):
+def score_topk_prologue_prep(kind, users_tab, user_ids, items, K, w_item, w_user=None, c=0.0, seeded_first_round=False,
+                             item_branch=None):
     """score_topk_prologue AND the fp16 filter's operand copies in one launch (macr_score_topk_prologue_prep): every row is
     read once.  For the score_topk call that follows with filter="f16", ws_ready=True, prep_ready=True and the same kind, c,
-    tables, K.  c: a float or a 1-element device tensor."""
+    tables, K.  c: a float or a 1-element device tensor.  item_branch (rows like `items`, or None: `items`): the table the
+    items' branch factors are computed from (macr_score_topk_prologue_prep_branch; LightGCN's rubi_ratings2)."""
     U = users_tab.shape[0] if user_ids is None else user_ids.numel()
     n_local, d = items.shape
     sig_i = torch.empty(n_local, dtype=_f32, device=items.device)
     sig_u = torch.empty(U, dtype=_f32, device=items.device) if w_user is not None else None
     ws = _topk_workspace(U, n_local, d, items.device)
     cv, cp = _c_args(c)
+    if item_branch is not None:
+        assert item_branch.shape == items.shape
+        check(_lib.lib().macr_score_topk_prologue_prep_branch(
+            kind, U, n_local, d, K, int(bool(seeded_first_round)), _ptr(items, _f32), _ptr(item_branch, _f32),
+            _ptr(w_item.reshape(-1), _f32), _ptr(sig_i), _ptr(users_tab, _f32), _ptr(user_ids, _i32, True),
+            _ptr(w_user.reshape(-1), _f32) if w_user is not None else None, _ptr(sig_u, _f32, True), cv, cp, _ptr(ws), ws.numel(),
+            _stream()))
+        return sig_i, sig_u
     check(_lib.lib().macr_score_topk_prologue_prep(kind, U, n_local, d, K, int(bool(seeded_first_round)),
                                                    _ptr(items, _f32), _ptr(w_item.reshape(-1), _f32), _ptr(sig_i),
                                                    _ptr(users_tab, _f32), _ptr(user_ids, _i32, True),

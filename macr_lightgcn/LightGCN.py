@@ -28,6 +28,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from utility.helper import early_stopping, ensureDir          # noqa: E402
 from utility.batch_test import *                              # noqa: E402,F401,F403  (args, data_generator, test ...)
+from utility.branch_ranking import test, test_sweep           # noqa: E402,F811  (+ --test rubi1 / rubi2)
 from macr_amd.lightgcn import LightGCN as _LightGCN           # noqa: E402
 from macr_amd.mf import Session                               # noqa: E402
 
@@ -221,7 +222,7 @@ def main(sweep=False):
                 say(perf_str, end='')
             if ret['hr'][0] > best_hr_norm:
                 best_hr_norm, best_epoch = ret['hr'][0], epoch
-        elif args.test == 'rubiboth':
+        elif args.test in ('rubiboth', 'rubi1', 'rubi2'):      # (the same loop over c, LightGCN.py:848-854)
             if main_rank:
                 print('Epoch %d' % epoch)
             best_hr = 0
@@ -241,7 +242,7 @@ def main(sweep=False):
                 best_c_hr, best_c_epoch = best_hr, epoch
             say(perf_str, end='')
         else:
-            raise NotImplementedError("--test %s is outside the MI355X hot path (normal | rubiboth)" % args.test)
+            raise NotImplementedError("--test %s is outside the MI355X hot path (normal | rubiboth | rubi1 | rubi2)" % args.test)
 
         cur_best_pre_0, stopping_step, should_stop = early_stopping(ret['hr'][0], cur_best_pre_0, stopping_step,
                                                                     expected_order='acc', flag_step=10)

@@ -1,6 +1,6 @@
 """Command-line flags of the LightGCN CLI -- same names, types and defaults as the reference's
 macr_lightgcn/utility/parser.py:10-104.  On the MI355X hot path: --alg_type lightgcn, --adj_type pre,
---loss {bpr,bce,bceboth}, --test {normal,rubiboth}; the remaining flags are accepted for compatibility.
+--loss {bpr,bce,bceboth,bce1,bce2}, --test {normal,rubiboth,rubi1,rubi2}; the remaining flags are accepted for compatibility.
 Additive: --seed, --sampler, --resume."""
 import argparse
 
@@ -36,10 +36,10 @@ _FLAGS = [
     ("base", float, -1., "(compat)"),
     ("log_interval", int, 10, "evaluate every N epochs"),
     ("only_test", int, 0, "(compat)"),
-    ("loss", None, 'bpr', "bpr | bce | bceboth  (bce1, bce2 are out of scope)"),
+    ("loss", None, 'bpr', "bpr | bce | bceboth | bce1 | bce2"),
     ("alpha", float, 1e-3, "weight of the item-branch loss"),
     ("beta", float, 1e-3, "weight of the user-branch loss"),
-    ("test", None, 'normal', "normal | rubiboth"),
+    ("test", None, 'normal', "normal | rubiboth | rubi1 | rubi2"),
     ("early_stop", int, 1, "1: stop after 10 evaluations without HR improvement"),
     ("start", float, -1., "LightGCN_tune.py: first c of the sweep"),
     ("end", float, 1., "LightGCN_tune.py: last c of the sweep"),
