@@ -54,6 +54,12 @@ extern "C" {
 #define MACR_LOSS_RUBIBCE_EGO 5  /* --loss bce2          LightGCN.py:463-493 (abi 16; LightGCN only): RUBIBCE whose branch logits
                                     read the EGO item rows e0_i.w, e0_j.w -- their gradient reaches those rows directly, not
                                     through the propagation; every MF and shard entry point refuses it as it refuses BPR_LGCN */
+#define MACR_LOSS_RUBIBPR     6  /* --train rubi        macr_mf/model.py:124-156 (abi 16; MF only): the two-branch BPR loss, a (B,B) kind
+                                    like RUBIBCE -- -mean_{r,c}(log(sigmoid(a[r] p[c] - b[r] n[c]))) - alpha mean(log(sigmoid(s_i - s_j))),
+                                    a = sigmoid(s_i), b = sigmoid(s_j); w trained, w_user untouched; no epsilon and no clamp (a cell
+                                    below about -88 overflows fp32: loss non-finite, gradient NaN, as in TF).  Taken wherever the MF
+                                    entry points take RUBIBCE, deferred and lazy modes included; every macr_shard_* entry point and
+                                    both LightGCN steps refuse it as they refuse RUBIBCE_EGO                                        */
 /* NORMALBCE, BPR and BPR_LGCN are the PER-PAIR kinds: no (B,B) term and no branch vectors (w, w_user untouched).  Every
  * entry point that takes NORMALBCE takes the per-pair kind of its model; every one that refuses NORMALBCE refuses them too,
  * with the same error code. */
@@ -116,13 +122,13 @@ typedef struct macr_hyper {
  *   losses     (dev) fp32[3] = {loss, mf_loss, reg_loss} of this step
  *   workspace  (dev) >= macr_mf_train_workspace_bytes(B, d) bytes, 256-B aligned
  *
- * loss_kind: NORMALBCE, RUBIBCEBOTH, RUBIBCE or BPR.
+ * loss_kind: NORMALBCE, RUBIBCEBOTH, RUBIBCE, BPR or RUBIBPR.
  * d must be 32, 64, 128 or 256.  B >= 1.  No host synchronisation; safe to
  * capture into a hipGraph.
  *
  * flags = 0: the call is one complete step (P, Q, w, wu and the slots are up to
  * date in stream order when it returns).
- * Deferred mode (rubibceboth, rubibce; the per-pair kinds: MACR_E_INVALID): the step's pass over ALL rows of P and Q
+ * Deferred mode (rubibceboth, rubibce, rubi; the per-pair kinds: MACR_E_INVALID): the step's pass over ALL rows of P and Q
  * (tf.train.AdamOptimizer moves every row every step) is bound by HBM, the
  * (B,B) loss kernel by the VALU; neither depends on the other across a step
  * boundary, so consecutive steps can overlap them:

@@ -226,7 +226,7 @@ __device__ __forceinline__ void finalize_losses(const LossArgs &L, int lane, dou
             mf = (float)(bce / Bd);
         } else {
             const float Lo = (float)(lo / (Bd * Bd)), Li = (float)(li / Bd), Lu = (float)(lu / Bd);
-            mf = (L.kind == MACR_LOSS_RUBIBCE || L.kind == MACR_LOSS_RUBIBCE_EGO) ? Lo + L.alpha * Li    // macr_mf/model.py:178
+            mf = (L.kind == MACR_LOSS_RUBIBCE || L.kind == MACR_LOSS_RUBIBCE_EGO || L.kind == MACR_LOSS_RUBIBPR) ? Lo + L.alpha * Li    // macr_mf/model.py:178, :149
                                              : Lo + L.alpha * Li + L.beta * Lu;               // :217
         }
         float regularizer = (float)(0.5 * sq);                  // tf.nn.l2_loss x3  (:219)
@@ -514,6 +514,9 @@ __global__ __launch_bounds__(256) void k_lazy_rows(long long n, const int32_t *_
 // ----------------------------------------------------------------------------
 // Window of the (B,B) kernel's 4-transcendental form in y = n*b (see k_bxb): shared with pair_fwd, which flags the columns outside it
 constexpr float kBxbYHi = 6.0f, kBxbYLoPairs = -60.0f, kBxbYLoSingle = -20.0f;
+// Window of the BPR cell's paired logarithm (k_bxb, run_tile_bpr): log2((1 + e^-Z1)(1 + e^-Z2)) needs the product finite,
+// (1 + e^40)^2 = 5.5e34 < FLT_MAX = 3.4e38 (at Z = -44.3 it is not)
+constexpr float kBprZLoPairs = -40.0f;
 constexpr int kNeutralTileMax = 8;      // a 64-column tile with more flagged columns than this is not neutralised (its wave decides as before)
 
 // Tables the deferred-mode forward needs to see one update ahead (below).
@@ -536,7 +539,7 @@ struct PendingAdam {
 // steps first (stamp + 1 .. pending step - 1, in registers), then the pending step as above.  The lane group also marks
 // its three rows (flag bit 1) so that the pass riding in this step's (B,B) launch brings them to the pending step IN
 // MEMORY before pair_bwd reads them in place.
-template <int LPR, int PENDING>
+template <int LPR, int PENDING, bool RUBIBPR = false>
 __global__ __launch_bounds__(256) void k_pair_fwd(
     int B, int Bp, const int32_t *__restrict__ u, const int32_t *__restrict__ i, const int32_t *__restrict__ j,
     const float *__restrict__ Usrc, const float *__restrict__ Isrc,
@@ -545,6 +548,9 @@ __global__ __launch_bounds__(256) void k_pair_fwd(
     int user_branch, const float *__restrict__ Bsrc = nullptr) {
     // Bsrc (MACR_LOSS_RUBIBCE_EGO, LightGCN --loss bce2): the item rows the branch logits si, sj read (the ego table),
     // NULL: the scored rows themselves
+    // RUBIBPR (MACR_LOSS_RUBIBPR, model.py:124-156): the item-branch term is -log(sig(si - sj)) (:146) and slot 6 of fwd holds
+    // 1 - sig(si - sj), what pair_bwd needs of it, in place of the constant sig(su) = 1 (stored through fabsf: the sign bit of
+    // this slot is the column flag of the BCE kinds, and 0/0 at si - sj < -88 is a NaN of either sign)
     constexpr int d = 4 * LPR;
     __shared__ float red[48];
     __shared__ float s_lr[PENDING == 2 ? kLazyRing : 1];
@@ -629,8 +635,14 @@ __global__ __launch_bounds__(256) void k_pair_fwd(
             // The SIGN of the stored sig(su) (a value in [0, 1]; its readers take fabsf) flags column t of the (B,B) term as outside
             // the window of the 4-transcendental form whatever its row (a, b <= 1): k_bxb takes such columns out of the rotation
             // (see "neutralised columns" there).  An array of its own cost pair_fwd 0.5 us for the extra store.
-            fwd[6 * (size_t)Bp + t] = (p < -20.0f || n > kBxbYHi || n < kBxbYLoPairs) ? -ssu : ssu;
-            litem = -logf(ssi + eps) + -logf((1.0f - ssj) + eps);
+            if (RUBIBPR) {
+                float hi, hj;                             // (+-(1 - sig(si - sj)), formed as PairLossBPR forms it)
+                litem = PairLossBPR::term(si, sj, 1.0f, hi, hj);
+                fwd[6 * (size_t)Bp + t] = fabsf(hj);
+            } else {
+                fwd[6 * (size_t)Bp + t] = (p < -20.0f || n > kBxbYHi || n < kBxbYLoPairs) ? -ssu : ssu;
+                litem = -logf(ssi + eps) + -logf((1.0f - ssj) + eps);
+            }
             luser = user_branch ? -logf(ssu + eps) + -logf((1.0f - ssu) + eps) : 0.0f;
         }
     }
@@ -749,7 +761,13 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 // blocks riding in the launch are bound by memory-level parallelism, and one more of their waves beside each (B,B) wave is worth
 // 0.3-0.5 us per step -- bxb+adam 19.12-19.41 -> 18.87-19.17 us, bxb alone 12.7-13.2 -> 12.1-12.6, same box (profiles/
 // r06_bxb_waves_ab.txt; seven waves spill and cost 4.5 us).  The lazy form (ADAM == 2) needs its registers: left alone.
-template <int R, bool FULL, int ADAM>
+// CELL: what a cell of the (B,B) matrix is.  kCellBce: the two BCE terms of rubibceboth / rubibce described above.  kCellBpr
+// (MACR_LOSS_RUBIBPR, macr_mf/model.py:138-144): ONE term per cell,
+//   Z[r,c] = a[r]*p[c] - b[r]*n[c],   L_ori = mean(-log(sig(Z)))   (no epsilon),
+// with the same launch shape, the same rotation and the same outputs (run_tile_bpr below); only the tile arithmetic differs, and
+// the neutralised-columns machinery -- a statement about the BCE window -- is not used (the caller launches with nneu = 0).
+constexpr int kCellBce = 0, kCellBpr = 1;
+template <int R, bool FULL, int ADAM, int CELL = kCellBce>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ADAM == 2 ? 4 : 6, 8))) void k_bxb(int B, int Bp, int ncb, int nbxb, const float *__restrict__ fwd,
                                              float *__restrict__ rowpart, float *__restrict__ colpart,
                                              float *__restrict__ lpart, AdamArgs adam, const StepScalars *scal,
@@ -1013,6 +1031,83 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ADAM == 2 ?
         acc = v2f{accx.x + accx.y, accy.x + accy.y};
         l2 = v2f{lsum, 0.f};
     };
+    // CELL == kCellBpr.  With e = e^-Z (one exp2 of -log2(e) Z, itself one packed multiply and one packed fma), dd = 1 + e:
+    //     -log(sig(Z)) = ln2 * log2(dd),      1 - sig(Z) = e * rcp(dd)  (= g: G = -g / B^2 is d L_ori / d Z)
+    // -- the reference's log(sigmoid(Z)) with its operations kept: e overflows where the reference's sigmoid reaches 0
+    // (Z < -88.7: loss +inf, g = inf * 0 = NaN, as in TF; nothing is clamped).  The sums keep k_bxb's signs and places:
+    //     acc = {sum_r g a, sum_r g b} -> colpart {-acc.x, acc.y} = B^2 {dp, dn},   dab = {sum_c g p, sum_c g n} -> rowpart
+    //     {-dab.x, dab.y} = B^2 {da, db}.
+    // Rows of a lane go in PAIRS (R = 2, 4), a packed register holding the same quantity of two rows: 8 packed, 2 plain and
+    // 5 transcendental instructions per two cells with ONE logarithm of dd1*dd2 (PAIRED) -- which overflows when
+    // Z1 + Z2 < -88 although each cell is finite, so a wave takes it only when every Z of its tile is above kBprZLoPairs (the
+    // bounds of the BCE window: |p| amax, |n| bmax over the wave's rows); else one logarithm per cell (6 per two cells).
+    // R = 1 is the same cell on plain registers (3 transcendentals), its row and column sums packed as {a, b} and {p, n}.
+    auto run_tile_bpr = [&](auto paired_t) {
+        constexpr bool PAIRED = decltype(paired_t)::value;
+        float lsum = 0.f;
+        if constexpr (R == 1) {
+            const float sa = ab[0].x * (-kLog2e), sb = ab[0].y * kLog2e;
+#pragma unroll 2
+            for (int k = 0; k < 64; ++k) {
+                const float e = __builtin_amdgcn_exp2f(fmaf(sb, cn.y, sa * cn.x));
+                float dd = e + 1.0f;
+                float g = e * __builtin_amdgcn_rcpf(dd);
+                if (!FULL) {
+                    const bool ok = rok[0] && cb * 256 + wid * 64 + ((lane + k) & 63) < B;
+                    g = ok ? g : 0.f; dd = ok ? dd : 1.0f;
+                }
+                lsum += __builtin_amdgcn_logf(dd);
+                dab[0] = __builtin_elementwise_fma(v2f{g, g}, cn, dab[0]);
+                acc = __builtin_elementwise_fma(v2f{g, g}, ab[0], acc);
+                cn.x = wave_rol1(cn.x); cn.y = wave_rol1(cn.y); acc.x = wave_rol1(acc.x); acc.y = wave_rol1(acc.y);
+            }
+        } else {
+            constexpr int H = R / 2 > 0 ? R / 2 : 1;
+            v2f sa[H], sb[H], a2[H], b2[H], dax[H], dby[H];
+            bool ok0[H], ok1[H];
+#pragma unroll
+            for (int h = 0; h < H; ++h) {
+                a2[h] = v2f{ab[2 * h].x, ab[(2 * h + 1) % R].x}; b2[h] = v2f{ab[2 * h].y, ab[(2 * h + 1) % R].y};
+                sa[h] = a2[h] * (-kLog2e); sb[h] = b2[h] * kLog2e;
+                dax[h] = v2f{0.f, 0.f}; dby[h] = v2f{0.f, 0.f};
+                ok0[h] = rok[2 * h]; ok1[h] = rok[(2 * h + 1) % R];
+            }
+            v2f accx = {0.f, 0.f}, accy = {0.f, 0.f};
+#pragma unroll 2
+            for (int k = 0; k < 64; ++k) {
+                bool colok = true;
+                if (!FULL) colok = cb * 256 + wid * 64 + ((lane + k) & 63) < B;
+                const v2f pp = {cn.x, cn.x}, nn = {cn.y, cn.y};
+#pragma unroll
+                for (int h = 0; h < H; ++h) {
+                    const v2f z = __builtin_elementwise_fma(sb[h], nn, sa[h] * pp);          // -log2(e) * Z of the two rows
+                    const v2f e = {__builtin_amdgcn_exp2f(z.x), __builtin_amdgcn_exp2f(z.y)};
+                    v2f dd = e + one;
+                    v2f g = e * v2f{__builtin_amdgcn_rcpf(dd.x), __builtin_amdgcn_rcpf(dd.y)};
+                    if (!FULL) {
+                        const bool k0 = ok0[h] && colok, k1 = ok1[h] && colok;
+                        g = v2f{k0 ? g.x : 0.f, k1 ? g.y : 0.f};
+                        dd = v2f{k0 ? dd.x : 1.0f, k1 ? dd.y : 1.0f};
+                    }
+                    if (PAIRED) lsum += __builtin_amdgcn_logf(dd.x * dd.y);
+                    else lsum += __builtin_amdgcn_logf(dd.x) + __builtin_amdgcn_logf(dd.y);
+                    dax[h] = __builtin_elementwise_fma(g, pp, dax[h]);
+                    dby[h] = __builtin_elementwise_fma(g, nn, dby[h]);
+                    accx = __builtin_elementwise_fma(g, a2[h], accx);
+                    accy = __builtin_elementwise_fma(g, b2[h], accy);
+                }
+                cn.x = wave_rol1(cn.x); cn.y = wave_rol1(cn.y);
+                accx.x = wave_rol1(accx.x); accx.y = wave_rol1(accx.y); accy.x = wave_rol1(accy.x); accy.y = wave_rol1(accy.y);
+            }
+#pragma unroll
+            for (int h = 0; h < H; ++h) {
+                dab[2 * h] = v2f{dax[h].x, dby[h].x};
+                if (2 * h + 1 < R) dab[2 * h + 1] = v2f{dax[h].y, dby[h].y};
+            }
+            acc = v2f{accx.x + accx.y, accy.x + accy.y};
+        }
+        l2 = v2f{-lsum, 0.f};                   // (the block sum below negates: the loss terms are +ln2 * log2(dd))
+    };
 #if defined(MACR_ABL_BXB_EXACT)
     const bool fast = false;
 #elif defined(MACR_ABL_BXB_FORCEFAST)
@@ -1033,9 +1128,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ADAM == 2 ?
     // <= 2e-6 relative on a loss that is a sum of positive terms (tolerance 1e-5); 2e-7 at y = 3, 1.1e-5 at y = 8.
     constexpr float YLO = R >= 2 ? kBxbYLoPairs : kBxbYLoSingle, YHI = kBxbYHi;
     const float xlo = cn.x * amax, yv = cn.y * bmax;
-    const bool fast = !__any(!(xlo >= -20.0f) || !(yv >= YLO) || !(yv <= YHI) || !(amax <= 1.0f) || !(bmax <= 1.0f));   // (NaN -> exact path)
+    bool out;
+    if constexpr (CELL == kCellBpr) {
+        // Z >= min(p,0) amax - max(n,0) bmax for every row of the wave; a NaN score or row factor (fmaxf drops NaNs) fails the test
+        bool nan_row = false;
+#pragma unroll
+        for (int q = 0; q < R; ++q) nan_row = nan_row || !(ab[q].x + ab[q].y == ab[q].x + ab[q].y);
+        out = nan_row || !(fminf(xlo, 0.f) - fmaxf(yv, 0.f) >= kBprZLoPairs) || !(cn.x == cn.x) || !(cn.y == cn.y);
+    } else {
+        out = !(xlo >= -20.0f) || !(yv >= YLO) || !(yv <= YHI) || !(amax <= 1.0f) || !(bmax <= 1.0f);    // (NaN -> exact path)
+    }
+    const bool fast = !__any(out);
 #endif
-    if (fast) {
+    if constexpr (CELL == kCellBpr) {
+        if constexpr (R == 1) run_tile_bpr(std::true_type{});             // (one row per lane: no shared logarithm, no window)
+        else if (fast) run_tile_bpr(std::true_type{});
+        else run_tile_bpr(std::false_type{});
+    } else if (fast) {
         if constexpr (R >= 2) run_tile_pairs(); else run_tile(std::true_type{});
     } else {
         run_tile(std::false_type{});
@@ -1122,7 +1231,7 @@ __device__ __forceinline__ void combine_positive_rows(const int *s_pos, const fl
 // EGO (MACR_LOSS_RUBIBCE_EGO, LightGCN --loss bce2): the branch logits read the rows of Bsrc (the ego table) -- the branch
 // terms dsi*w, dsj*w leave the gradient rows of Isrc and go, one scalar per item row, to sbr[row] += dsi (dsj) (the caller
 // adds sbr[row]*w to the ego row's gradient); w's gradient is formed from the Bsrc rows
-template <int D, bool EGO = false>
+template <int D, bool EGO = false, bool RUBIBPR = false>
 __global__ __launch_bounds__(256) void k_pair_bwd(
     int B, int Bp, int nrb, int ncb, const int32_t *__restrict__ perm, const int32_t *__restrict__ u,
     const int32_t *__restrict__ i, const int32_t *__restrict__ j, const float *__restrict__ Usrc,
@@ -1133,6 +1242,8 @@ __global__ __launch_bounds__(256) void k_pair_bwd(
     float alpha, float beta, float coef, float *adam_pow, StepScalars *scal, float lr, float b1, float b2,
     LossArgs L, int32_t *cnt_pos, LazyState *lazy = nullptr, int nneu = 0, const float *__restrict__ Bsrc = nullptr,
     float *sbr = nullptr) {
+    // RUBIBPR (MACR_LOSS_RUBIBPR): slot 6 of fwd holds h = 1 - sig(si - sj) (k_pair_fwd) and sig(su) is 1; the item-branch
+    // term -alpha mean(log(sig(si - sj))) gives dsi -= (alpha/B) h, dsj += (alpha/B) h in place of the two BCE derivatives
     constexpr int EPL = WaveRow<D>::EPL;
     __shared__ float s_w[4][2][D];
     __shared__ float s_gi[kChunkT][D];
@@ -1237,8 +1348,10 @@ __global__ __launch_bounds__(256) void k_pair_bwd(
         }
         ssj = __shfl(ssi, (lane & 48) + 1, kWave); ssu = __shfl(ssi, (lane & 48) + 2, kWave); ssi = __shfl(ssi, lane & 48, kWave);
         dp *= inv_b2; dn *= inv_b2; da *= inv_b2; db *= inv_b2;
-        const float dsi_own = da * (ssi * (1.0f - ssi)) * ssu + (alpha * invB) * dneglog_sig(ssi, eps);
-        const float dsj_own = db * (ssj * (1.0f - ssj)) * ssu + (alpha * invB) * dneglog_1msig(ssj, eps);
+        const float hbpr = ssu;
+        if (RUBIBPR) ssu = 1.0f;
+        const float dsi_own = da * (ssi * (1.0f - ssi)) * ssu + (alpha * invB) * (RUBIBPR ? -hbpr : dneglog_sig(ssi, eps));
+        const float dsj_own = db * (ssj * (1.0f - ssj)) * ssu + (alpha * invB) * (RUBIBPR ? hbpr : dneglog_1msig(ssj, eps));
         const float dsu_own = (da * ssi + db * ssj) * (ssu * (1.0f - ssu)) +
                               (beta * invB) * (dneglog_sig(ssu, eps) + dneglog_1msig(ssu, eps));
 #pragma unroll
@@ -1436,7 +1549,7 @@ __global__ __launch_bounds__(256) void k_pair_normal_stage(
 // rubibceboth backward; see k_pair_bwd for the arithmetic.  The last block does the step bookkeeping.
 // EGO: see k_pair_bwd<D, true>; the branch scalars dsi, dsj are STAGED like the gradient rows -- sst[o1], sst[o2] -- and
 // summed per row in list order by k_seg_reduce (the determinism of the rows)
-template <int LPR, bool EGO = false>
+template <int LPR, bool EGO = false, bool RUBIBPR = false>
 __global__ __launch_bounds__(256) void k_pair_bwd_stage(
     int B, int Bp, int nrb, int ncb, const int32_t *__restrict__ u, const int32_t *__restrict__ i,
     const int32_t *__restrict__ j, const float *__restrict__ Usrc, const float *__restrict__ Isrc,
@@ -1445,6 +1558,7 @@ __global__ __launch_bounds__(256) void k_pair_bwd_stage(
     float *__restrict__ wpart, float alpha, float beta, float coef, float *adam_pow, StepScalars *scal, float lr,
     float b1, float b2, LossArgs L, const uint32_t *__restrict__ place = nullptr, int Bnorm = 0, LazyState *lazy = nullptr,
     int nneu = 0, const float *__restrict__ Bsrc = nullptr, float *__restrict__ sst = nullptr) {
+    // RUBIBPR: see k_pair_bwd
     // Bnorm > 0: the launch covers a SLICE of a batch of Bnorm triples (row-sharded training, macr_shard_backward_slice): u/i/j,
     // fwd, rowpart and colpart arrive offset to the slice, B is its length, the means are taken over the whole batch
     constexpr int d = 4 * LPR, RPB = RowGroup<LPR>::kRowsPerBlock;
@@ -1478,9 +1592,10 @@ __global__ __launch_bounds__(256) void k_pair_bwd_stage(
         da += dan; db += dbn;
         dp = group_sum<LPR>(dp) * inv_b2; dn = group_sum<LPR>(dn) * inv_b2;
         da = group_sum<LPR>(da) * inv_b2; db = group_sum<LPR>(db) * inv_b2;
-        const float ssi = fwd[4 * (size_t)Bp + t], ssj = fwd[5 * (size_t)Bp + t], ssu = fabsf(fwd[6 * (size_t)Bp + t]);    // (the sign: a flag of pair_fwd)
-        const float dsi = da * (ssi * (1.0f - ssi)) * ssu + (alpha * invB) * dneglog_sig(ssi, eps);
-        const float dsj = db * (ssj * (1.0f - ssj)) * ssu + (alpha * invB) * dneglog_1msig(ssj, eps);
+        const float ssi = fwd[4 * (size_t)Bp + t], ssj = fwd[5 * (size_t)Bp + t], s6 = fabsf(fwd[6 * (size_t)Bp + t]);    // (the sign: a flag of pair_fwd)
+        const float ssu = RUBIBPR ? 1.0f : s6;
+        const float dsi = da * (ssi * (1.0f - ssi)) * ssu + (alpha * invB) * (RUBIBPR ? -s6 : dneglog_sig(ssi, eps));
+        const float dsj = db * (ssj * (1.0f - ssj)) * ssu + (alpha * invB) * (RUBIBPR ? s6 : dneglog_1msig(ssj, eps));
         const float dsu = (da * ssi + db * ssj) * (ssu * (1.0f - ssu)) +
                           (beta * invB) * (dneglog_sig(ssu, eps) + dneglog_1msig(ssu, eps));
         const int ru = u[t], ri = i[t], rj = j[t];
@@ -1826,7 +1941,8 @@ struct PairWs {
     size_t bytes;
 };
 
-static PairWs carve_pair_ws(void *base, int B, int d, bool force_staged = false) {
+// neutral = false (MACR_LOSS_RUBIBPR): no neutral blocks in the (B,B) launch, whatever the batch
+static PairWs carve_pair_ws(void *base, int B, int d, bool force_staged = false, bool neutral = true) {
     PairWs w;
     const int lpr = d / 4, rpb = 256 / lpr;
     w.Bp = (int)align_up((size_t)B, 256);
@@ -1834,7 +1950,7 @@ static PairWs carve_pair_ws(void *base, int B, int d, bool force_staged = false)
     w.nrb = w.Bp / (64 * w.rows);
     w.ncb = w.Bp / 256;
     static const bool no_neutral = getenv("MACR_BXB_NEUTRAL") && getenv("MACR_BXB_NEUTRAL")[0] == '0';      // A/B switch
-    w.nneu = (!force_staged && B % 256 == 0 && !no_neutral) ? 1 : 0;     // (full batches; the row-sharded step keeps the plain launch)
+    w.nneu = (!force_staged && B % 256 == 0 && !no_neutral && neutral) ? 1 : 0;     // (full batches; the row-sharded step keeps the plain launch)
     w.ncbx = w.ncb + w.nneu;
     w.nblk_pair = (B + rpb - 1) / rpb;
     w.staged = force_staged || use_staging(B);
@@ -1873,7 +1989,7 @@ static PairWs carve_pair_ws(void *base, int B, int d, bool force_staged = false)
 }
 
 // grid: nbxb (B,B) blocks, then the blocks that group the batch (small path), then the pending Adam blocks
-template <int R>
+template <int R, int CELL = kCellBce>
 static void launch_bxb_rows(const PairWs &ws, int B, const AdamArgs *pending, long long n_adam_blocks,
                             const BatchSort &sort, hipStream_t st) {
     const int nbxb = ws.ncb * ws.nrb, nsort = (sort.B + kBucketSpan - 1) / kBucketSpan + sort.nneu * ws.nrb;    // (+ the neutral blocks)
@@ -1883,17 +1999,17 @@ static void launch_bxb_rows(const PairWs &ws, int B, const AdamArgs *pending, lo
 #endif
     if (pending && pending->lazy) {
         const unsigned grid = (unsigned)(nbxb + nsort + n_adam_blocks);
-        if (full) k_bxb<R, true, 2><<<grid, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, *pending, ws.scal, sort);
-        else      k_bxb<R, false, 2><<<grid, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, *pending, ws.scal, sort);
+        if (full) k_bxb<R, true, 2, CELL><<<grid, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, *pending, ws.scal, sort);
+        else      k_bxb<R, false, 2, CELL><<<grid, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, *pending, ws.scal, sort);
     } else if (pending) {
         const unsigned grid = (unsigned)(nbxb + nsort + n_adam_blocks);
-        if (full) k_bxb<R, true, 1><<<grid, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, *pending, ws.scal, sort);
-        else      k_bxb<R, false, 1><<<grid, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, *pending, ws.scal, sort);
+        if (full) k_bxb<R, true, 1, CELL><<<grid, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, *pending, ws.scal, sort);
+        else      k_bxb<R, false, 1, CELL><<<grid, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, *pending, ws.scal, sort);
     } else {
         AdamArgs none;
         none.n_seg = 0;
-        if (full) k_bxb<R, true, 0><<<nbxb + nsort, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, none, ws.scal, sort);
-        else      k_bxb<R, false, 0><<<nbxb + nsort, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, none, ws.scal, sort);
+        if (full) k_bxb<R, true, 0, CELL><<<nbxb + nsort, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, none, ws.scal, sort);
+        else      k_bxb<R, false, 0, CELL><<<nbxb + nsort, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, none, ws.scal, sort);
     }
 }
 
@@ -1965,7 +2081,9 @@ static int launch_pair(int kind, int B, int d, int n_urows, int n_irows, const i
                        const float *Bsrc = nullptr, float *sbr = nullptr) {
     const int grid = ws.nblk_pair;
     const int user_branch = kind == MACR_LOSS_RUBIBCEBOTH;
+    const int rubibpr = kind == MACR_LOSS_RUBIBPR;
     const bool ego = Bsrc != nullptr;
+    MACR_REQUIRE(!rubibpr || (ws.nneu == 0 && !ego), MACR_E_INVALID, "pair: the BPR cell has no neutral blocks and no ego branch");
     BatchSort sort = batch_sort_args(ws, B, u, i, j);
     if (ws.staged || loss_only) sort.B = 0;
     sort.outflag = ws.fwd + 6 * (size_t)ws.Bp; sort.nneu = ws.nneu; sort.ncbx = ws.ncbx;      // neutralised columns of the (B,B) launch (pair_fwd flags them)
@@ -2008,23 +2126,28 @@ static int launch_pair(int kind, int B, int d, int n_urows, int n_irows, const i
         MACR_CHECK_LAUNCH("pair_normal", st);
         return MACR_OK;
     }
+    // RB: the kernels' template flag of MACR_LOSS_RUBIBPR (one argument list per launch, both values of the flag)
+#define MACR_DISPATCH_RUBIBPR(...)                                          \
+    if (rubibpr) { constexpr bool RB = true; __VA_ARGS__; } else { constexpr bool RB = false; __VA_ARGS__; }
     if (pa && pa->lazy) {
-        MACR_DISPATCH_LPR(d, (k_pair_fwd<LPR, 2><<<grid, 256, 0, st>>>(B, ws.Bp, u, i, j, Usrc, Isrc, w, wu, ws.fwd,
-                                                                      ws.part, reg_on_gathered, ws.gw, *pa, user_branch)));
+        MACR_DISPATCH_RUBIBPR(MACR_DISPATCH_LPR(d, (k_pair_fwd<LPR, 2, RB><<<grid, 256, 0, st>>>(B, ws.Bp, u, i, j, Usrc, Isrc, w, wu, ws.fwd,
+                                                                                            ws.part, reg_on_gathered, ws.gw, *pa, user_branch))));
     } else if (pa) {
-        MACR_DISPATCH_LPR(d, (k_pair_fwd<LPR, 1><<<grid, 256, 0, st>>>(B, ws.Bp, u, i, j, Usrc, Isrc, w, wu, ws.fwd,
-                                                                      ws.part, reg_on_gathered, ws.gw, *pa, user_branch)));
+        MACR_DISPATCH_RUBIBPR(MACR_DISPATCH_LPR(d, (k_pair_fwd<LPR, 1, RB><<<grid, 256, 0, st>>>(B, ws.Bp, u, i, j, Usrc, Isrc, w, wu, ws.fwd,
+                                                                                            ws.part, reg_on_gathered, ws.gw, *pa, user_branch))));
     } else {
         PendingAdam none = {};
-        MACR_DISPATCH_LPR(d, (k_pair_fwd<LPR, 0><<<grid, 256, 0, st>>>(B, ws.Bp, u, i, j, Usrc, Isrc, w, wu, ws.fwd,
-                                                                      ws.part, reg_on_gathered, ws.gw, none, user_branch, Bsrc)));
+        MACR_DISPATCH_RUBIBPR(MACR_DISPATCH_LPR(d, (k_pair_fwd<LPR, 0, RB><<<grid, 256, 0, st>>>(B, ws.Bp, u, i, j, Usrc, Isrc, w, wu, ws.fwd,
+                                                                                            ws.part, reg_on_gathered, ws.gw, none, user_branch, Bsrc))));
     }
     MACR_CHECK_LAUNCH("pair_fwd", st);
-    switch (ws.rows) {
-        case 1: launch_bxb_rows<1>(ws, B, pending, n_pending_blocks, sort, st); break;
-        case 2: launch_bxb_rows<2>(ws, B, pending, n_pending_blocks, sort, st); break;
-        default: launch_bxb_rows<4>(ws, B, pending, n_pending_blocks, sort, st); break;
-    }
+    MACR_DISPATCH_RUBIBPR(
+        constexpr int CELL = RB ? kCellBpr : kCellBce;
+        switch (ws.rows) {
+            case 1: launch_bxb_rows<1, CELL>(ws, B, pending, n_pending_blocks, sort, st); break;
+            case 2: launch_bxb_rows<2, CELL>(ws, B, pending, n_pending_blocks, sort, st); break;
+            default: launch_bxb_rows<4, CELL>(ws, B, pending, n_pending_blocks, sort, st); break;
+        });
     MACR_CHECK_LAUNCH(pending ? "bxb+adam" : "bxb", st);
     if (loss_only) return MACR_OK;
     LossArgs L;
@@ -2042,10 +2165,10 @@ static int launch_pair(int kind, int B, int d, int n_urows, int n_irows, const i
         return launch_ref_sort_reduce(B, d, n_urows, n_irows, u, i, j, gU, gI, tU, tI, ws, st, nullptr, sst, sbr);
     }
     if (ws.staged) {
-        MACR_DISPATCH_LPR(d, (k_pair_bwd_stage<LPR><<<ws.nblk_bwd + 1, 256, 0, st>>>(
+        MACR_DISPATCH_RUBIBPR(MACR_DISPATCH_LPR(d, (k_pair_bwd_stage<LPR, false, RB><<<ws.nblk_bwd + 1, 256, 0, st>>>(
                                  B, ws.Bp, ws.nrb, ws.ncb, u, i, j, Usrc, Isrc, w, wu, ws.fwd, ws.rowpart, ws.colpart, ws.stage,
                                  ws.gw, hp->alpha, hp->beta, coef, adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, L,
-                                 listed ? rs.free_val : nullptr, 0, tick, ws.nneu)));
+                                 listed ? rs.free_val : nullptr, 0, tick, ws.nneu))));
         MACR_CHECK_LAUNCH("pair_bwd", st);
         if (listed) return launch_seg_index(B, d, n_urows, n_irows, rs, true, gU, gI, tU, tI, ws, st);
         return launch_ref_sort_reduce(B, d, n_urows, n_irows, u, i, j, gU, gI, tU, tI, ws, st, sv_sorted);
@@ -2057,11 +2180,12 @@ static int launch_pair(int kind, int B, int d, int n_urows, int n_irows, const i
                                                                             ws.scal, hp->lr, hp->beta1, hp->beta2, L, cnt_pos, tick,
                                                                             ws.nneu, Bsrc, sbr)));
     } else {
-        MACR_DISPATCH_D(d, (k_pair_bwd<D><<<ws.nblk_bwd + 1, 256, 0, st>>>(B, ws.Bp, ws.nrb, ws.ncb, ws.perm, ws.us, ws.is, ws.js,
-                                                                          Usrc, Isrc, w, wu, ws.fwd, ws.rowpart, ws.colpart, gU,
-                                                                          gI, tU, tI, ws.gw, hp->alpha, hp->beta, coef, adam_pow,
-                                                                          ws.scal, hp->lr, hp->beta1, hp->beta2, L, cnt_pos, tick, ws.nneu)));
+        MACR_DISPATCH_RUBIBPR(MACR_DISPATCH_D(d, (k_pair_bwd<D, false, RB><<<ws.nblk_bwd + 1, 256, 0, st>>>(
+                                 B, ws.Bp, ws.nrb, ws.ncb, ws.perm, ws.us, ws.is, ws.js, Usrc, Isrc, w, wu, ws.fwd, ws.rowpart, ws.colpart, gU,
+                                 gI, tU, tI, ws.gw, hp->alpha, hp->beta, coef, adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, L, cnt_pos,
+                                 tick, ws.nneu))));
     }
+#undef MACR_DISPATCH_RUBIBPR
     MACR_CHECK_LAUNCH("pair_bwd", st);
     return MACR_OK;
 }
@@ -2151,7 +2275,7 @@ static int mf_train_step(int loss_kind, int B, int d, int n_users, int n_items, 
                          float *adam_pow, const macr_hyper *hp, float *losses, int flags, const macr_lazy_adam *lz,
                          void *workspace, size_t workspace_bytes, void *stream) {
     MACR_REQUIRE(loss_kind == MACR_LOSS_NORMALBCE || loss_kind == MACR_LOSS_RUBIBCEBOTH || loss_kind == MACR_LOSS_RUBIBCE ||
-                     loss_kind == MACR_LOSS_BPR, MACR_E_INVALID, "mf_train_step: loss_kind=%d", loss_kind);
+                     loss_kind == MACR_LOSS_BPR || loss_kind == MACR_LOSS_RUBIBPR, MACR_E_INVALID, "mf_train_step: loss_kind=%d", loss_kind);
     MACR_REQUIRE(B > 0 && n_users > 0 && n_items > 0, MACR_E_INVALID, "mf_train_step: B=%d n_users=%d n_items=%d", B,
                  n_users, n_items);
     MACR_REQUIRE(dim_supported(d), MACR_E_UNSUPPORTED, "mf_train_step: d=%d not in {32,64,128,256}", d);
@@ -2163,17 +2287,17 @@ static int mf_train_step(int loss_kind, int B, int d, int n_users, int n_items, 
     MACR_REQUIRE(!flags || !is_pair_loss(loss_kind), MACR_E_INVALID,
                  "mf_train_step: deferred mode exists for the (B,B) losses only (flags=%d)", flags);
     MACR_REQUIRE(!lz || !is_pair_loss(loss_kind), MACR_E_UNSUPPORTED,
-                 "mf_train_step_lazy: the lazy pass rides in the (B,B) launch (rubibceboth, rubibce)");
+                 "mf_train_step_lazy: the lazy pass rides in the (B,B) launch (rubibceboth, rubibce, rubi)");
     if (int e = validate_hyper(hp, "mf_train_step")) return e;
     if (lz) if (int e = validate_lazy(lz, true, true, "mf_train_step_lazy")) return e;
-    PairWs ws = carve_pair_ws(workspace, B, d);
+    PairWs ws = carve_pair_ws(workspace, B, d, false, loss_kind != MACR_LOSS_RUBIBPR);
     MACR_REQUIRE(workspace_bytes >= ws.bytes, MACR_E_WORKSPACE, "mf_train_step: workspace %zu < %zu bytes",
                  workspace_bytes, ws.bytes);
     MACR_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, MACR_E_INVALID,
                  "mf_train_step: workspace must be 256-byte aligned");
     hipStream_t st = as_stream(stream);
     const float coef = hp->decay / (float)hp->batch_size_cfg;       // d reg / d row  (model.py:219-221)
-    const bool rubi = !is_pair_loss(loss_kind);                  // the (B,B) losses: rubibceboth, rubibce
+    const bool rubi = !is_pair_loss(loss_kind);                  // the (B,B) losses: rubibceboth, rubibce, rubi (BPR)
     LossArgs L;
     L.part = ws.part; L.n_part = rubi ? ws.nblk_pair : ws.nblk_bwd;
     L.part2 = nullptr; L.n_part2 = 0;
@@ -2234,7 +2358,7 @@ static int mf_train_flush(int loss_kind, int B, int d, int n_users, int n_items,
                           float *mP, float *vP, float *mQ, float *vQ, float *mw, float *vw, float *mwu,
                           float *vwu, float *gP, float *gQ, int32_t *touchedP, int32_t *touchedQ,
                           const macr_hyper *hp, const macr_lazy_adam *lz, void *workspace, size_t workspace_bytes, void *stream) {
-    MACR_REQUIRE(loss_kind == MACR_LOSS_RUBIBCEBOTH || loss_kind == MACR_LOSS_RUBIBCE, MACR_E_INVALID,
+    MACR_REQUIRE(loss_kind == MACR_LOSS_RUBIBCEBOTH || loss_kind == MACR_LOSS_RUBIBCE || loss_kind == MACR_LOSS_RUBIBPR, MACR_E_INVALID,
                  "mf_train_flush: loss_kind=%d has no deferred mode", loss_kind);
     MACR_REQUIRE(B > 0 && n_users > 0 && n_items > 0, MACR_E_INVALID, "mf_train_flush: B=%d n_users=%d n_items=%d", B,
                  n_users, n_items);
@@ -2243,7 +2367,7 @@ static int mf_train_flush(int loss_kind, int B, int d, int n_users, int n_items,
                      touchedQ && workspace, MACR_E_INVALID, "mf_train_flush: null pointer");
     if (int e = validate_hyper(hp, "mf_train_flush")) return e;
     if (lz) if (int e = validate_lazy(lz, true, true, "mf_train_flush_lazy")) return e;
-    PairWs ws = carve_pair_ws(workspace, B, d);
+    PairWs ws = carve_pair_ws(workspace, B, d, false, loss_kind != MACR_LOSS_RUBIBPR);
     MACR_REQUIRE(workspace_bytes >= ws.bytes, MACR_E_WORKSPACE, "mf_train_flush: workspace %zu < %zu bytes",
                  workspace_bytes, ws.bytes);
     AdamArgs a;

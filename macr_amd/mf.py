@@ -6,8 +6,9 @@ exercise:
     --train rubibceboth -> opt_two_bce_both / loss_two_bce_both / ...                (:71-74, :185-222)
     --train rubibce     -> opt_two_bce / loss_two_bce / ...  (item branch only)      (:67-69, :158-183)
     --train normal      -> opt / loss / mf_loss / reg_loss  (BPR)                     (:49-57, :264-275)
+    --train rubi        -> the two-branch BPR loss of opt_two (fast path only: no fetch) (:64-66, :124-156)
     --test  normal      -> batch_ratings                                             (:45)
-    --test  rubi        -> rubi_ratings_both (rubibceboth) | rubi_ratings (other losses) + update_c   (:199, :141, :313)
+    --test  rubi        -> rubi_ratings_both (rubibceboth) | rubi_ratings (rubibce, rubi) + update_c   (:199, :141, :313)
     direct_minus_ratings(_both) (:142, :201) are served too (test(model_type="direct_minus_c"))
 The reference builds a TF1 graph and the CLI talks to it through
 `sess.run(fetches, feed_dict)`; here the same attribute names are plain fetch
@@ -15,7 +16,7 @@ handles and `Session.run` dispatches them to the C-ABI kernels, so a caller
 written against the reference keeps working.  The fast path (`train_step`,
 `Evaluator`) avoids the per-step host synchronisation `sess.run` implies.
 
-Everything else in model.py (rubi / userc losses, BIASMF,
+Everything else in model.py (userc losses, BIASMF,
 IPS_BPRMF, CausalE) is out of scope and raises NotImplementedError.
 """
 import math
@@ -48,10 +49,12 @@ def xavier_uniform(shape, generator, device):
 
 class BPRMF(object):
     _TRAIN = {"normalbce": ("bce", ops.LOSS_NORMALBCE), "rubibceboth": ("two_bce_both", ops.LOSS_RUBIBCEBOTH),
-              "rubibce": ("two_bce", ops.LOSS_RUBIBCE), "normal": ("", ops.LOSS_BPR)}
+              "rubibce": ("two_bce", ops.LOSS_RUBIBCE), "normal": ("", ops.LOSS_BPR), "rubi": (None, ops.LOSS_RUBIBPR)}
+    # (suffix None: the kind has no fetch handles -- `--train rubi` is served by train_step() only; `opt_two` stays among the
+    # unsupported fetches of the session shim)
     # optimizers created the first time their loss trains (their Adam slots and gradient scratch are table-sized: a run that
     # never trains BPR allocates nothing for it)
-    _ON_DEMAND = (ops.LOSS_BPR,)
+    _ON_DEMAND = (ops.LOSS_BPR, ops.LOSS_RUBIBPR)
 
     def __init__(self, args, data_config, device=None, seed=12345, weights=None):
         self.n_users = data_config['n_users']
@@ -81,6 +84,8 @@ class BPRMF(object):
             if kind not in self._ON_DEMAND:
                 self._opt[kind] = ops.MFState(self.weights['user_embedding'], self.weights['item_embedding'],
                                               self.w, self.w_user, hyper, self.batch_size)
+            if suffix is None:
+                continue
             for role in ("opt", "loss", "mf_loss", "reg_loss"):        # opt_bce ... ; the BPR graph's plain opt, loss ... (:49-57)
                 name = role + "_" + suffix if suffix else role
                 setattr(self, name, Fetch(name, role, kind))
@@ -135,7 +140,7 @@ class BPRMF(object):
     # ------------------------------------------------------------------ fast path
     def kind_of(self, train):
         if train not in self._TRAIN:
-            raise NotImplementedError("--train %s is not on the MI355X hot path (normal | normalbce | rubibce | rubibceboth)" % train)
+            raise NotImplementedError("--train %s is not on the MI355X hot path (normal | normalbce | rubi | rubibce | rubibceboth)" % train)
         return self._TRAIN[train][1]
 
     def _state(self, kind):
@@ -155,7 +160,7 @@ class BPRMF(object):
 
     def train_step(self, kind, batch, losses=None, defer=False):
         """batch: (3,B) int32 device tensor.  Returns the (3,) device tensor {loss, mf_loss, reg_loss};
-        no host synchronisation.  defer=True lets consecutive rubibceboth steps overlap the dense Adam pass of
+        no host synchronisation.  defer=True lets consecutive steps of a (B,B) loss (rubibceboth, rubibce, rubi) overlap the dense Adam pass of
         one step with the (B,B) kernel of the next (MACR_STEP_DEFER); the parameters are then only up to date
         after sync(), which every reader below calls."""
         for k, st in self._opt.items():
@@ -254,7 +259,10 @@ class ShardedBPRMF(object):
 
     def kind_of(self, train):
         if train not in self._TRAIN:
-            raise NotImplementedError("--train %s is not on the MI355X hot path (normal | normalbce | rubibce | rubibceboth)" % train)
+            raise NotImplementedError("--train %s is not on the MI355X hot path (normal | normalbce | rubi | rubibce | rubibceboth)" % train)
+        if self._TRAIN[train][1] == ops.LOSS_RUBIBPR:
+            raise NotImplementedError("--train rubi has no row-sharded step (--row_shard 1): the sharded (B,B) entry points carry no "
+                                      "loss kind; train it unsharded")
         return self._TRAIN[train][1]
 
     def _model(self, kind):

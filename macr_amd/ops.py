@@ -10,7 +10,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (LOSS_NORMALBCE, LOSS_RUBIBCEBOTH, LOSS_RUBIBCE, LOSS_BPR, LOSS_BPR_LGCN, LOSS_RUBIBCE_EGO, SCORE_NORMAL, SCORE_RUBI_BOTH, SCORE_RUBI,  # noqa: F401
+from ._lib import (LOSS_NORMALBCE, LOSS_RUBIBCEBOTH, LOSS_RUBIBCE, LOSS_BPR, LOSS_BPR_LGCN, LOSS_RUBIBCE_EGO, LOSS_RUBIBPR, SCORE_NORMAL, SCORE_RUBI_BOTH, SCORE_RUBI,  # noqa: F401
                    SCORE_DIRECT_MINUS, SCORE_DIRECT_MINUS_BOTH, MAX_TOPK,
                    Hyper, MacrError, check, is_pair_loss)
 
@@ -667,7 +667,7 @@ class MFState(object):
 
     def step(self, kind, u, i, j, losses=None, defer=False):
         """One training step; u,i,j int32 device tensors.  Returns the (3,) device loss tensor.
-        defer=True (rubibceboth, rubibce): leave the dense Adam pass pending so that the next step runs it under its
+        defer=True (rubibceboth, rubibce, rubi): leave the dense Adam pass pending so that the next step runs it under its
         (B,B) kernel (include/macr_hip.h, MACR_STEP_DEFER); call flush() before reading the parameters."""
         B = u.numel()
         if self.pending_B and self.pending_B != B:

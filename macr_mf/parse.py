@@ -1,6 +1,6 @@
 """Command-line flags of the MF CLI -- same names, types and defaults as the reference's
 macr_mf/parse.py:3-92, so existing launch lines keep working.  Only --model mf with
---train {normal,normalbce,rubibce,rubibceboth} / --test {normal,rubi} runs on the MI355X hot path; flags
+--train {normal,normalbce,rubi,rubibce,rubibceboth} / --test {normal,rubi} runs on the MI355X hot path; flags
 that belong to out-of-scope baselines are accepted for compatibility.
 Additive flags (not in the reference): --seed, --sampler."""
 import argparse
@@ -10,7 +10,7 @@ _FLAGS = [
     ("data_path", None, './data/', "directory that holds <dataset>/train.txt, test.txt"),
     ("dataset", None, 'movielens_ml_1m', "dataset name (addressa, gowalla, ml_10m, yelp2018, globe, ...)"),
     ("source", None, 'normal', "normal | dice (dice is out of scope)"),
-    ("train", None, 'normalbce', "normal (BPR) | normalbce | rubibce | rubibceboth  (--test rubi: the two branch losses)"),
+    ("train", None, 'normalbce', "normal (BPR) | normalbce | rubi (two-branch BPR) | rubibce | rubibceboth  (--test rubi: the three branch losses)"),
     ("test", None, 'normal', "normal | rubi"),
     ("valid_set", None, 'test', "test | valid"),
     ("alpha", float, 1e-3, "weight of the item-branch loss"),

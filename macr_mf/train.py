@@ -4,6 +4,8 @@
         --log_interval 10 --lr 0.001 --train normalbce --test normal
     python ./macr_mf/train.py --dataset gowalla --batch_size 4096 --cuda 0 --saveID 0 --log_interval 10 \
         --lr 0.001 --check_c 1 --c 40 --train rubibceboth --test rubi --alpha 1e-2 --beta 1e-3
+    python ./macr_mf/train.py --dataset addressa --batch_size 1024 --cuda 0 --saveID 2 --log_interval 10 \
+        --lr 0.001 --c 40 --train rubi --test rubi --alpha 1e-2
 
 Same flags, stdout/log line formats, early stopping and checkpoint directory naming as the
 reference (macr_mf/train.py:332-611); the training step and the evaluator run on the HIP
@@ -251,7 +253,7 @@ def main(sweep=False):
             if main_rank:
                 print('Epoch %d' % epoch)
             if ops.is_pair_loss(kind):
-                raise NotImplementedError("--test rubi needs a branch loss (--train rubibceboth | rubibce)")
+                raise NotImplementedError("--test rubi needs a branch loss (--train rubibceboth | rubibce | rubi)")
             c_values = np.linspace(args.start, args.end, args.step) if sweep else [args.c]
             best = (0, 0, 0, 0, 0.0)               # train.py:540-544: bests start at 0
             # tune.py:545-578: one test() per c; here the values of a sweep share the listing pass in groups of four
