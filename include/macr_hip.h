@@ -194,6 +194,9 @@ int macr_mf_train_flush(int loss_kind, int B, int d, int n_users, int n_items,
  *                        references through gP/gQ), and updates w, w_user
  * All five take the SAME workspace (>= macr_shard_workspace_bytes(B, d), 256-B aligned,
  * contents preserved between the calls of one step); adam_pow as in macr_mf_train_step.
+ * A rank may own no row of a table (fewer rows than ranks: n_users_loc or n_items_loc = 0): the pointers of that table
+ * (rows, slots, gradient scratch, flags, stamps) may then be NULL, gather and apply serve the case, and a rank that owns
+ * no row at all under a per-pair loss has nothing to update (macr_shard_apply returns MACR_OK without an Adam launch).
  * -------------------------------------------------------------------------*/
 size_t macr_shard_workspace_bytes(int B, int d);
 int macr_shard_gather(int B, int d, const float *P_loc, int u_lo, int u_stride, int n_users_loc, const float *Q_loc,
@@ -217,7 +220,9 @@ int macr_shard_backward(int loss_kind, int B, int d, const float *rows3, const f
  *                              (dev) fp32[3][n][d], losses of the whole batch, this slice's share of the branch-vector gradient
  *                              rows (returned region: sum over the ranks)
  *   macr_shard_stage           where macr_shard_apply reads gradient rows: (dev) fp32[3][B][d] inside the workspace, row
- *                              role * B + t; the caller fills the rows of the references this rank owns */
+ *                              role * B + t; the caller fills the rows of the references this rank owns
+ *   macr_shard_slice           [t0, t1) of a rank: the positions of its row blocks, cut at B (a rank whose blocks lie in the padding
+ *                              above B has an empty slice); with fewer row blocks than ranks, B * rank / world .. B * (rank + 1) / world */
 int macr_shard_slice(int B, int d, int rank, int world, int *t0, int *t1);
 int macr_shard_forward_slice(int loss_kind, int B, int d, int t0, int n, const float *rows3_slice, const float *w,
                              const float *wu, void **region, size_t *region_bytes, void *workspace,

@@ -1689,7 +1689,8 @@ __global__ __launch_bounds__(256) void k_seg_reduce(int n, int n_users, uint32_t
                 else sbr[row] = sb;
             }
         }
-        if (g.sub == 0 && key0 != prev && tU) (is_user ? tU : tI)[row] = 1;
+        int32_t *tf = is_user ? tU : tI;           // (a table without flags -- or without rows on this rank -- has none to set)
+        if (g.sub == 0 && key0 != prev && tf) tf[row] = 1;
     }
 }
 
@@ -2621,13 +2622,16 @@ static int shard_gather(int B, int d, const float *P_loc, const float *mP, const
                         const float *Q_loc, const float *mQ, const float *vQ, int i_lo, int i_stride, int n_items_loc,
                         const int32_t *u, const int32_t *i, const int32_t *j, const macr_hyper *hp, const macr_lazy_adam *lz,
                         float *rows3, void *stream) {
-    MACR_REQUIRE(B > 0 && dim_supported(d) && P_loc && Q_loc && u && i && j && rows3 && u_lo >= 0 && i_lo >= 0 && u_stride >= 1 &&
-                     i_stride >= 1 && n_users_loc >= 0 && n_items_loc >= 0, MACR_E_INVALID, "shard_gather: bad argument");
+    // (a rank may own no row of a table -- fewer rows than ranks: its pointers for that table may be null, nothing reads them)
+    MACR_REQUIRE(B > 0 && dim_supported(d) && u && i && j && rows3 && u_lo >= 0 && i_lo >= 0 && u_stride >= 1 && i_stride >= 1 &&
+                     n_users_loc >= 0 && n_items_loc >= 0 && (P_loc || n_users_loc == 0) && (Q_loc || n_items_loc == 0),
+                 MACR_E_INVALID, "shard_gather: bad argument");
     const Owned ou = {u_lo, u_stride, n_users_loc}, oi = {i_lo, i_stride, n_items_loc};
     LazyTable tp = {P_loc, mP, vP, nullptr}, tq = {Q_loc, mQ, vQ, nullptr};
     const int grid = grid_for(3LL * B * (d / 4));
     if (lz) {
-        MACR_REQUIRE(mP && vP && mQ && vQ && hp, MACR_E_INVALID, "shard_gather_lazy: null pointer");
+        MACR_REQUIRE(((mP && vP) || n_users_loc == 0) && ((mQ && vQ) || n_items_loc == 0) && hp, MACR_E_INVALID,
+                     "shard_gather_lazy: null pointer");
         if (int e = validate_lazy(lz, n_users_loc > 0, n_items_loc > 0, "shard_gather_lazy")) return e;
         tp.stamp = lz->stampP; tq.stamp = lz->stampQ;
         MACR_DISPATCH_LPR(d, (k_rows_gather_owned<LPR, true><<<grid, 256, 0, as_stream(stream)>>>(
@@ -2787,7 +2791,12 @@ extern "C" int macr_shard_slice(int B, int d, int rank, int world, int *t0, int 
     MACR_REQUIRE(B > 0 && dim_supported(d) && world >= 1 && rank >= 0 && rank < world && t0 && t1, MACR_E_INVALID, "shard_slice: bad argument");
     const PairWs ws = carve_pair_ws(nullptr, B, d, true);
     const int rows = 64 * ws.rows;
-    const long long a = (long long)ws.nrb * rank / world * rows, b = (long long)ws.nrb * (rank + 1) / world * rows;
+    long long a = (long long)ws.nrb * rank / world * rows, b = (long long)ws.nrb * (rank + 1) / world * rows;
+    // Fewer row blocks than ranks (a small batch on many ranks): block-aligned slices would hand one rank most of the batch and most
+    // ranks nothing, and that rank would receive nearly all 3B rows.  The slices need not follow the blocks -- the forward state is
+    // summed over the ranks before the (B,B) term reads it, and the slice kernels address positions one by one -- so the positions
+    // are spread evenly: a rank moves ~ 2 * 3B/W rows for any B and W.
+    if (ws.nrb < world) { a = (long long)B * rank / world; b = (long long)B * (rank + 1) / world; }
     *t0 = (int)(a < B ? a : B);
     *t1 = (int)(b < B ? b : B);
     return MACR_OK;
@@ -2873,9 +2882,10 @@ static int shard_apply(int loss_kind, int B, int d, int n_users_loc, int n_items
                        float *wu, float *mP, float *vP, float *mQ, float *vQ, float *mw, float *vw, float *mwu, float *vwu,
                        float *gP, float *gQ, int32_t *touchedP, int32_t *touchedQ, const macr_hyper *hp,
                        const macr_lazy_adam *lz, void *workspace, size_t workspace_bytes, void *stream) {
-    MACR_REQUIRE(n_users_loc >= 0 && n_items_loc >= 0 && u_stride >= 1 && i_stride >= 1 && u && i && j && P && Q && w && wu && mP &&
-                     vP && mQ && vQ && mw && vw && mwu && vwu && gP && gQ && touchedP && touchedQ, MACR_E_INVALID,
-                 "shard_apply: bad argument");
+    // (a rank may own no row of a table: that table's pointers may then be null -- no key names it, no Adam segment is built for it)
+    MACR_REQUIRE(n_users_loc >= 0 && n_items_loc >= 0 && u_stride >= 1 && i_stride >= 1 && u && i && j && w && wu && mw && vw &&
+                     mwu && vwu && ((P && mP && vP && gP && touchedP) || n_users_loc == 0) &&
+                     ((Q && mQ && vQ && gQ && touchedQ) || n_items_loc == 0), MACR_E_INVALID, "shard_apply: bad argument");
     if (int e = validate_hyper(hp, "shard_apply")) return e;
     if (lz) if (int e = validate_lazy(lz, n_users_loc > 0, n_items_loc > 0, "shard_apply_lazy")) return e;
     MACR_SHARD_COMMON("shard_apply");
@@ -2938,6 +2948,7 @@ static int shard_apply(int loss_kind, int B, int d, int n_users_loc, int n_items
         MACR_CHECK_LAUNCH("adam_lazy", st);
         return MACR_OK;
     }
+    if (nb == 0) return MACR_OK;                  // no row of either table and no branch vector to train: an empty grid is no launch
     if (indexed) {
         k_adam_dense<true><<<(unsigned)nb, 256, 0, st>>>(a, ws.scal, L);
         MACR_CHECK_LAUNCH("adam_indexed", st);

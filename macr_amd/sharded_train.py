@@ -141,8 +141,10 @@ class HipBackend(object):
         """(n, d) rows of the local table `table` ("P" / "Q") as of the current step; rows: int32 local indices, < 0 = a zero row"""
         o, L = self.ops, self._lib.lib()
         rows = rows.to(torch.int32).contiguous()
-        out = torch.empty((rows.numel(), self.d), dtype=torch.float32, device=self.device)
         th, m, v, st = ((shard._P, shard._mP, shard._vP, shard.stP) if table == "P" else (shard._Q, shard._mQ, shard._vQ, shard.stQ))
+        if th.shape[0] == 0:                # a rank without a row of this table: every index names the zero row
+            return torch.zeros((rows.numel(), self.d), dtype=torch.float32, device=self.device)
+        out = torch.empty((rows.numel(), self.d), dtype=torch.float32, device=self.device)
         self._lib.check(L.macr_lazy_rows(rows.numel(), self.d, o._ptr(rows), o._ptr(th), o._ptr(m), o._ptr(v), o._ptr(st),
                                          o._ptr(shard.lazy_state), ctypes.byref(self.hyper), o._ptr(out), o._stream()))
         return out
@@ -460,9 +462,12 @@ class RowShardedMF(object):
                     be.lazy_rows(self, "Q", torch.where(user, neg, self.own_i.local_index(sr))))     # (x + 0: exact)
         else:
             is_user = (send_ref < B).unsqueeze(1)
-            from_p = self._P[self.own_u.local_index(sr).clamp(0, max(self._P.shape[0] - 1, 0))]     # (both tables are indexed for every
-            from_q = self._Q[self.own_i.local_index(sr).clamp(0, max(self._Q.shape[0] - 1, 0))]     # reference: n_send rows each, no branch)
-            send = torch.where(is_user, from_p, from_q)
+
+            def rows_of(table, own):            # (both tables are indexed for every reference: n_send rows each, no branch)
+                if table.shape[0] == 0:         # a rank without a row of this table owns none of the references to it
+                    return table.new_zeros((n_send, d))
+                return table[own.local_index(sr).clamp(0, table.shape[0] - 1)]
+            send = torch.where(is_user, rows_of(self._P, self.own_u), rows_of(self._Q, self.own_i))
         recv = torch.empty((n_recv, d), dtype=self._P.dtype, device=self._P.device)
         self._all_to_all(recv, send.contiguous(), recv_counts, send_counts, "rows_a2a")
         # arrival order -> (role, position in the slice)

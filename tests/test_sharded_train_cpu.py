@@ -283,3 +283,45 @@ def test_route_tables_are_consistent():
             off_r = int(tabs[0][:q_, p_].sum())
             assert torch.equal(sends[q_][off_s:off_s + n], recvs[p_][off_r:off_r + n]), (q_, p_)
             off_s += n
+
+
+def test_split_step_slices_partition_the_batch_and_bound_the_wire():
+    """macr_shard_slice (host arithmetic of the library): the slices of the ranks tile [0, B) in rank order for any B, W and d, they
+    follow the (B,B) row blocks while there are at least as many blocks as ranks, and with fewer blocks than ranks (B = 100 on 8
+    ranks: four blocks of 64) they spread the positions evenly, so that no rank's exchange exceeds the 2 * 3B/W + 3B/4 rows the
+    split step is held to"""
+    import ctypes
+    from macr_amd import _lib
+    L = _lib.lib()
+
+    def slices(B, d, W):
+        out = []
+        for r in range(W):
+            t0, t1 = ctypes.c_int(), ctypes.c_int()
+            assert L.macr_shard_slice(B, d, r, W, ctypes.byref(t0), ctypes.byref(t1)) == 0
+            out.append((t0.value, t1.value))
+        return out
+
+    for B, d, W in ((300, 64, 3), (100, 32, 8), (1500, 128, 5), (4096, 64, 3), (4096, 64, 16), (4352, 64, 3), (257, 256, 2),
+                    (777, 64, 3), (8192, 128, 8), (64, 32, 16), (1, 32, 16)):
+        s = slices(B, d, W)
+        assert s[0][0] == 0 and s[-1][1] == B and all(a[1] == b[0] for a, b in zip(s, s[1:])) and all(t0 <= t1 for t0, t1 in s), (B, W, s)
+    assert slices(300, 64, 3) == [(0, 128), (128, 300), (300, 300)]          # eight 64-row blocks: 2 / 3 / 3, the last three above B
+    assert slices(4096, 64, 16) == [(256 * r, 256 * r + 256) for r in range(16)]
+    assert slices(100, 32, 8) == [(100 * r // 8, 100 * (r + 1) // 8) for r in range(8)]
+
+    class Slices(SplitOracleBackend):
+        def slice_of(self, B, rank, world):
+            return slices(B, self.d, world)[rank]
+
+    rs = np.random.RandomState(5)
+    n_users, n_items, d, B, W = 5, 77, 32, 100, 8
+    P, Q = torch.zeros((n_users, d)), torch.zeros((n_items, d))
+    u = torch.from_numpy(rs.choice(n_users, B, replace=True).astype(np.int32))
+    i = torch.from_numpy((rs.zipf(1.3, B) % n_items).astype(np.int32))
+    j = torch.from_numpy(rs.randint(0, n_items, B).astype(np.int32))
+    for r in range(W):
+        m = sharded_train.RowShardedMF(P, Q, torch.zeros(d), torch.zeros(d), Slices(1, d, **HYP), rank=r, world=W)
+        c = m.route(u, i, j)[0]
+        wire = int(c[r].sum() - c[r, r]) + int(c[:, r].sum() - c[r, r])
+        assert wire < 2 * 3 * B // W + 3 * B // 4, (r, wire)
