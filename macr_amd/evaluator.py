@@ -10,16 +10,30 @@ kernel -> column means.  Nothing U x N ever leaves the device (or exists).
 
 Both reference evaluators batch the users by BATCH_SIZE; every per-user result
 is independent of the batching, so all query users are ranked in one pass.
+
+Three parts: WHAT the next evaluation tries (seeds or a sampling pass, which candidate filter) is eval_policy.py's
+state machine, replaced -- never mutated -- in `self._policy`; HOW a ranking is launched travels as arguments
+(rank_local: seeded, mode, repair_of, filter), and the same arguments are the graph-cache key; the graph cache itself
+is _captured / _replay.
 """
 import os
 
 import numpy as np
 import torch
 
-from . import ops, sharding
-from . import _lib as _lib_consts
+from . import _lib, eval_policy, ops, sharding
 
-_LP_FILTERS = ("bf16", "f16")       # reduced-precision candidate filters (fp32 re-scoring; include/macr_hip.h MACR_EVAL_FILTER_*)
+
+class Ranked(tuple):
+    """(vals, idx) of rank_local, and `.seeded`: the ranking took its thresholds from the previous one's candidates"""
+    def __new__(cls, vals, idx, seeded):
+        self = tuple.__new__(cls, (vals, idx))
+        self.seeded = seeded
+        return self
+
+
+def _ptrs(*tensors):
+    return tuple(None if t is None else t.data_ptr() for t in tensors)
 
 
 class Evaluator(object):
@@ -38,8 +52,8 @@ class Evaluator(object):
         # candidate filter of the listing pass, an argument of every ranking call (include/macr_hip.h MACR_EVAL_FILTER_*): "f16" (default, round 6) =
         # one fp16 number per operand on the fp16 matrix cores, "bf16" = two-term bf16 products on the bf16 matrix cores -- both
         # with fp32 re-scoring of the best candidates -- "f32" = fp32 products throughout.  The ranking is the fp32 ranking bit
-        # for bit whichever it is; MACR_EVAL_FILTER in the environment overrides the default; the policy below steps down
-        # f16 -> bf16 -> f32 where a model's scores are packed closer than a filter resolves.
+        # for bit whichever it is; MACR_EVAL_FILTER in the environment overrides the default; the policy (eval_policy.py) steps
+        # down f16 -> bf16 -> f32 where a model's scores are packed closer than a filter resolves.
         self.filter = os.environ.get("MACR_EVAL_FILTER", "f16").strip().lower()
         ops.eval_filter_code(self.filter)         # a typo in the environment is refused here, by name
         # One GPU, graph replays: an evaluation launches the FIRST ROUND of the ranking only and writes its means and the
@@ -56,26 +70,19 @@ class Evaluator(object):
         fold = os.environ.get("MACR_EVAL_FOLD", "p").strip().lower()
         self.fold_prologue, self.fold_metrics = fold in ("1", "p"), fold in ("1", "m")
         self.fold_prep = os.environ.get("MACR_EVAL_FOLD_PREP", "1") != "0"       # (A/B switch of macr_score_topk_prologue_prep)
-        self._topk_mode = None                    # None: the complete call; "first" / "repair": its two halves
-        self._repair_bufs = None
-        self._last_entry = None
-        self._host_out = {}
+        self._policy = eval_policy.State()        # seed / filter back-offs: _seed_skip ... _bf16_backoff below read and replace it
         self.fast_stats = {"fast": 0, "redone": 0}
+        self._last_info = None
         self._graphs = {}
         self._graph_misses = 0
-        # seeding policy: thresholds come from the previous ranking unless that went badly last time
-        self._seeded_now = True                   # what the ranking about to be launched does (if it has seeds at all)
-        self._seed_skip, self._seed_backoff = 0, 1
-        # filter policy (the same shape): a bf16-filter evaluation that ended in the exact kernel -- candidate lists overflowed in
-        # both rounds: scores packed tighter at the top than the filter's error bound resolves, e.g. a catalogue of a million
-        # barely trained items under c = 40 -- cost 2-3x an fp32-filter evaluation; the next 1, 2, 4 ... 16 evaluations take the
-        # fp32 filter before bf16 is tried again.  The ranking is the same either way.
-        self._bf16_skip, self._bf16_backoff = 0, 1
-        # ... and one tier above it: the fp16 filter's margin is 12x the bf16 filter's.  An UNSEEDED fp16 evaluation that had
-        # to list query blocks again (lists that overflowed under a threshold less that margin: scores at the top closer
-        # together than fp16 resolves, e.g. (y - c) sig_i sig_u with c = 30 on barely trained rows of d = 128), or one that
-        # ended in the exact kernel, sends the next 1, 2, 4 ... 16 evaluations to the bf16 filter (whose own back-off leads on to fp32).
-        self._f16_skip, self._f16_backoff = 0, 1
+        self._graph_misses_by_shape = {}
+        self._host_out = {}                       # (flavour, Ks) -> pinned means of the first-round path
+        self._seeds = {}                          # _seed_key -> (U, SEED_WIDTH) ids the last ranking of that shard left
+        self._uses_seeds = {}                     # _shape_uses_seeds
+        self._mean_ws = {}                        # len(Ks) -> scratch of macr_metrics_mf_mean
+        self._c_sweep = {}                        # group size -> the device array of a sweep's values of c
+        self._c_dev = torch.zeros(1, dtype=torch.float32, device=device)         # _c_scalar
+        self._c_host = None
         self._stats = torch.zeros(2, dtype=torch.int32, device=device)          # macr_score_topk stats of the last ranking
         self._stats_host = torch.zeros(2, dtype=torch.int32)
         self._stats_first = torch.zeros(2, dtype=torch.int32)          # written by the first-round ranking's own kernel
@@ -105,36 +112,44 @@ class Evaluator(object):
         local_lists = [[(g - own.lo) // own.stride for g in row if g >= own.lo and (g - own.lo) % own.stride == 0
                         and (g - own.lo) // own.stride < own.n] for row in self._mask_lists]
         self._mask_local = ops.CSR.from_lists(local_lists, self.device)
-        self.__dict__.pop("_seeds", None)
+        self._seeds = {}
+
+    def _shard_range(self, n_rows):
+        """(lo, hi) of this rank's item rows, given the rows of the table the caller holds"""
+        if self._local_own is not None:
+            return 0, self._local_own.n
+        if self.local_items_range is not None:
+            return tuple(self.local_items_range)
+        return sharding.item_shard_range(n_rows, *sharding.world())
 
     def _shard(self, items_tab):
         """(lo, hi, this rank's rows of the item table)"""
-        if self._local_own is not None:
-            assert items_tab.shape[0] == self._local_own.n
-            return 0, self._local_own.n, items_tab
-        if self.local_items_range is not None:
-            lo, hi = self.local_items_range
+        lo, hi = self._shard_range(items_tab.shape[0])
+        if self._local_own is not None or self.local_items_range is not None:
             assert items_tab.shape[0] == hi - lo
             return lo, hi, items_tab
-        rank, ws = sharding.world()
-        lo, hi = sharding.item_shard_range(items_tab.shape[0], rank, ws)
         return lo, hi, items_tab[lo:hi]
 
     # ------------------------------------------------------------------ ranking
-    def rank_local(self, kind, users_tab, user_ids, items_tab, K, w=None, wu=None, c=0.0, branch=None):
-        """This rank's item shard: (val, idx) of shape (U,K) with GLOBAL item ids.
+    def rank_local(self, kind, users_tab, user_ids, items_tab, K, w=None, wu=None, c=0.0, branch=None, *,
+                   seeded=True, mode=None, repair_of=None, filter=None):
+        """This rank's item shard: Ranked (val, idx) of shape (U,K) with GLOBAL item ids.
         users_tab/items_tab: full embedding tables (replicated on every rank); a rank scores only its contiguous
         item shard.  branch (None: items_tab): the table, shaped and sharded like items_tab, the items' branch factors
-        sigmoid(row . w) come from (LightGCN's rubi_ratings2: the ego item rows)."""
+        sigmoid(row . w) come from (LightGCN's rubi_ratings2: the ego item rows).
+        seeded: take the thresholds from the seeds, if there are any; mode: None = the complete ranking, "first" / "repair" =
+        its two halves (repair_of: the first round's outputs and workspace); filter: None = filter_now."""
         ws = sharding.world()[1]
         lo, hi, items_local = self._shard(items_tab)
         branch_local = items_local if branch is None else self._shard(branch)[2]
+        filter = filter or self.filter_now
         sig_u = sig_i = None
         U = self.n_queries
         both = kind in (ops.SCORE_RUBI_BOTH, ops.SCORE_DIRECT_MINUS_BOTH)
+        mask = self._mask_local if self._local_own is not None else self.mask
         # one ranking call that initialises its own workspace: the branch factors and that initialisation are ONE launch
         # (macr_score_topk_prologue, below, once it is known whether the call is seeded)
-        fold = (kind != ops.SCORE_NORMAL and U <= self.max_queries_per_pass and self._topk_mode != "repair"
+        fold = (kind != ops.SCORE_NORMAL and U <= self.max_queries_per_pass and mode != "repair"
                 and items_local.shape[1] == users_tab.shape[1] and self.fold_prologue)
         if fold:
             pass
@@ -149,23 +164,19 @@ class Evaluator(object):
             # Seeds: the ids this shard returned last time (same queries, tables that moved by a few training steps).
             # Their exact current scores bound every query's K-th best score from below far more tightly than a
             # sampling pass does, for a tenth of its time (k_tau_seed); the ranking itself does not depend on them.
-            # Seeds the tables have moved away from (early epochs) cost a repair round, so the evaluator watches how
-            # many query blocks were listed twice (_seed_feedback) and goes back to the sampling pass for a while.
-            seeds = self.__dict__.setdefault("_seeds", {})
-            use = (self.use_seeds and ws == 1 and K <= _lib_consts.MAX_TOPK_FUSED       # (the wide ranking takes no seeds)
-                   and self._shape_uses_seeds(hi - lo, items_tab.shape[1]))
-            skey = (K, lo, hi) + (() if branch is None else (branch.data_ptr(),))     # (rubi1 and rubi2 rank differently)
-            seed = seeds.get(skey) if use else None
-            seeded = self._ranked_seeded = seed is not None and self._seeded_now
+            # Seeds the tables have moved away from (early epochs) cost a repair round, so the policy watches how
+            # many query blocks were listed twice (eval_policy.py) and goes back to the sampling pass for a while.
+            thresholds = K <= _lib.MAX_TOPK_FUSED and self._shape_uses_seeds(hi - lo, items_tab.shape[1])
+            use = self.use_seeds and ws == 1 and thresholds       # (the wide ranking takes no seeds)
+            skey = self._seed_key(K, lo, hi, branch)
+            seed = self._seeds.get(skey) if use else None
+            seeded = seed is not None and seeded
             if use and seed is None:
-                seed = seeds[skey] = torch.full((U, ops.SEED_WIDTH), -1, dtype=torch.int32, device=self.device)
+                seed = self._seeds[skey] = torch.full((U, ops.SEED_WIDTH), -1, dtype=torch.int32, device=self.device)
             # the ranking leaves its best SEED_WIDTH candidates per query in `seed` (in place): the next ranking's seeds
-            mask = self._mask_local if self._local_own is not None else self.mask
-            mode = self._topk_mode
             # under the fp16 filter the prologue also writes the listing pass's operand copies: every row read once (the tables are
             # cold after a log interval of training) -- not for a catalogue small enough to list everything, which runs no filter
-            fold_prep = (fold and self.fold_prep and self.filter_now == "f16" and K <= _lib_consts.MAX_TOPK_FUSED
-                         and self._shape_uses_seeds(hi - lo, items_tab.shape[1]))
+            fold_prep = fold and self.fold_prep and filter == "f16" and thresholds
             if fold_prep:
                 sig_i, sig_u = ops.score_topk_prologue_prep(kind, users_tab, user_ids, items_local, K, w, wu if both else None, c,
                                                             seeded_first_round=seeded and mode == "first",
@@ -173,93 +184,62 @@ class Evaluator(object):
             elif fold:
                 # (the prologue reads its item rows for the branch factors only: the branch table stands there)
                 sig_i, sig_u = ops.score_topk_prologue(users_tab, user_ids, branch_local, K, w, wu if both else None,
-                                                       seeded_first_round=seeded and mode == "first", filter=self.filter_now)
+                                                       seeded_first_round=seeded and mode == "first", filter=filter)
             vals, idx = ops.score_topk(kind, users_tab, user_ids, items_local, K, sig_u, sig_i, c, mask, lo,
                                        seed=seed if seeded else None, seed_out=seed,
                                        stats=self._stats_first if mode else self._stats, first_round=mode == "first",
-                                       repair_of=self._repair_bufs if mode == "repair" else None, filter=self.filter_now,
+                                       repair_of=repair_of if mode == "repair" else None, filter=filter,
                                        ws_ready=fold, prep_ready=fold_prep)
         else:
             # the ranking workspace (candidate lists, mask bitmap) grows with the number of queries: rank them in
             # chunks; every query is independent of the chunking
-            parts = []
+            seeded, parts = False, []
             for a in range(0, U, self.max_queries_per_pass):
                 b = min(U, a + self.max_queries_per_pass)
                 uid = user_ids[a:b] if user_ids is not None else torch.arange(a, b, dtype=torch.int32, device=self.device)
-                mask = self._mask_local if self._local_own is not None else self.mask
                 parts.append(ops.score_topk(kind, users_tab, uid, items_local, K, None if sig_u is None else sig_u[a:b],
-                                            sig_i, c, mask.row_range(a, b), lo, filter=self.filter_now))
+                                            sig_i, c, mask.row_range(a, b), lo, filter=filter))
             vals = torch.cat([p[0] for p in parts], dim=1)
             idx = torch.cat([p[1] for p in parts], dim=1)
         if self._local_own is not None:           # local row -> item id (the order by id within the shard is the same either way)
             own = self._local_own
             idx = torch.where(idx >= 0, idx * own.stride + own.lo, idx)
-        return vals, idx
+        return Ranked(vals, idx, seeded)
 
     def _seed_feedback(self):
-        """Decide, before a ranking is launched, whether it takes its thresholds from the seeds.  The previous seeded
-        ranking reports whether blocks of 256 queries had to be listed twice because a seeded threshold was too loose
-        (macr_score_topk stats).  The repair round costs about as much as an unseeded ranking however few blocks it
-        lists, so one of them means the model still moves too far between two evaluations for seeds to pay (early
-        epochs): the next 1, 2, 4 ... 16 evaluations use the sampling pass before seeds are tried again.  The choice only
-        moves time around: every mode returns the same ranking."""
-        # Several ranks: no seeds.  The policy's state is per shard, so ranks would switch between the seeded and the
-        # sampled launch sequence -- and capture the other graph, with its extra warm-up collectives -- at different
-        # evaluations: mismatched all-gathers.  (A 1/8 shard's sampling pass is 13 us; there is little to win.)
-        if not self.use_seeds or sharding.world()[1] > 1:
-            self._seeded_now = False
-            return False
-        if self._stats_evt is not None:
+        """Complete path: whether the ranking about to be launched takes its thresholds from the seeds
+        (eval_policy.seed_complete), once the previous seeded ranking's stats -- if a copy is in flight -- have been read.
+        The choice only moves time around: every mode returns the same ranking."""
+        world = sharding.world()[1]
+        relisted = None
+        if self._stats_evt is not None and eval_policy.seeds_allowed(self.use_seeds, world):
             self._stats_evt.synchronize()         # normally long complete: the caller has read the previous metrics
             self._stats_evt = None
             if self._last_seeded:
-                relisted, fell_back = int(self._stats_host[0]), int(self._stats_host[1])
-                if relisted > self._relist_tolerance():
-                    self._seed_skip = self._seed_backoff
-                    self._seed_backoff = min(16, 2 * self._seed_backoff)
-                else:
-                    self._seed_backoff = 1
-        if self._seed_skip > 0:
-            self._seed_skip -= 1
-            self._seeded_now = False
-        else:
-            self._seeded_now = True
-        return self._seeded_now
+                relisted = int(self._stats_host[0])
+        seeded, self._policy = eval_policy.seed_complete(self._policy, self.use_seeds, world, relisted,
+                                                         eval_policy.relist_tolerance(self.n_queries))
+        return seeded
 
     @property
     def filter_now(self):
         """the candidate filter of the ranking about to be launched: `filter`, or "f32" while a reduced-precision filter
         ("bf16", "f16") is backed off"""
-        if self.filter == "f16" and self._f16_skip == 0:
-            return "f16"
-        if self.filter in _LP_FILTERS:
-            return "f32" if self._bf16_skip > 0 else "bf16"
-        return self.filter
-
-    def _relist_tolerance(self):
-        """blocks of 256 queries a seeded ranking may list twice before the seeds count as stale: none up to 63 blocks (a repair
-        round costs what an unseeded ranking costs there), one per 64 blocks beyond -- on 100 000 queries a handful of
-        re-listed blocks is a few queries with degenerate scores (every item tied), not a model that moved away from its seeds,
-        and the sampling pass would cost every block more than their repair does"""
-        return ((self.n_queries + 255) // 256) // 64
+        return eval_policy.filter_now(self.filter, self._policy)
 
     def _shape_uses_seeds(self, n_local, d):
         """False for shards small enough that the ranking lists every unmasked item (no thresholds to seed)"""
         key = (n_local, d)
-        cache = self.__dict__.setdefault("_uses_seeds", {})
-        if key not in cache:
-            from . import _lib
-            cache[key] = bool(_lib.lib().macr_score_topk_uses_seeds(self.n_queries, n_local, d))
-        return cache[key]
+        if key not in self._uses_seeds:
+            self._uses_seeds[key] = bool(_lib.lib().macr_score_topk_uses_seeds(self.n_queries, n_local, d))
+        return self._uses_seeds[key]
+
+    @staticmethod
+    def _seed_key(K, lo, hi, branch):
+        return (K, lo, hi) + (() if branch is None else (branch.data_ptr(),))       # (rubi1 and rubi2 rank differently)
 
     def _has_seeds(self, K, n_items, branch=None):
-        bk = () if branch is None else (branch.data_ptr(),)
-        if self._local_own is not None:
-            return (K, 0, self._local_own.n) + bk in self.__dict__.get("_seeds", {})
-        if self.local_items_range is not None:
-            return (K,) + tuple(self.local_items_range) + bk in self.__dict__.get("_seeds", {})
-        rank, ws = sharding.world()
-        return (K,) + tuple(sharding.item_shard_range(n_items, rank, ws)) + bk in self.__dict__.get("_seeds", {})
+        return self._seed_key(K, *self._shard_range(n_items), branch) in self._seeds
 
     def _stats_readback(self, seeded):
         """after a ranking was launched: its stats travel to the host behind it (no synchronisation here)"""
@@ -272,10 +252,9 @@ class Evaluator(object):
     def rank(self, kind, users_tab, user_ids, items_tab, K, w=None, wu=None, c=0.0, fill_masked=False, branch=None):
         """Top-K item ids for every query user: (val (U,K), idx (U,K), cnt (U,)); the shards' top-K are all-gathered
         (one collective) and merged."""
-        self._seed_feedback()
-        self._ranked_seeded = False
-        vals, idx = self.rank_local(kind, users_tab, user_ids, items_tab, K, w, wu, c, branch)
-        self._stats_readback(self._ranked_seeded)
+        ranked = self.rank_local(kind, users_tab, user_ids, items_tab, K, w, wu, c, branch, seeded=self._seed_feedback())
+        self._stats_readback(ranked.seeded)
+        vals, idx = ranked
         fill = self.mask if fill_masked else None
         if sharding.world()[1] == 1:
             return ops.topk_merge(vals, idx, fill)
@@ -294,30 +273,26 @@ class Evaluator(object):
         """(W,U,K) lists (splits of one shard, or the gathered shards) -> column means of the per-user metrics.
         out: optional pinned host tensor the last kernel writes the means to."""
         if flavour == "mf":
+            if vals.shape[0] == 1:
+                ix, cnt = idx[0], None    # one sorted list per query: nothing to merge (the metrics kernel counts a list's ids itself)
+            else:
+                _, ix, cnt = ops.topk_merge(vals, idx)
+            if not self.fold_metrics:
+                return ops.colmean(ops.metrics_mf(ix, cnt, self.gt, list(Ks)), out=out)         # (U,4,nK) float64 -> (4,nK)
             # metrics and their means over the queries in one launch (macr_metrics_mf_mean); its scratch is this evaluator's
             # own (a captured graph bakes the address in)
-            if not self.fold_metrics:
-                if vals.shape[0] == 1:
-                    return ops.colmean(ops.metrics_mf(idx[0], None, self.gt, list(Ks)), out=out)
-                _, ix, cnt = ops.topk_merge(vals, idx)
-                return ops.colmean(ops.metrics_mf(ix, cnt, self.gt, list(Ks)), out=out)         # (U,4,nK) float64 -> (4,nK)
-            mws = self.__dict__.setdefault("_mean_ws", {})
-            if len(Ks) not in mws:
-                mws[len(Ks)] = ops.metrics_mf_mean_workspace(idx.shape[1], len(Ks), idx.device)
-            if vals.shape[0] == 1:
-                # one sorted list per query: nothing to merge (the metrics kernel counts a list's ids itself)
-                return ops.metrics_mf_mean(idx[0], None, self.gt, list(Ks), mws[len(Ks)], out=out)
-            _, ix, cnt = ops.topk_merge(vals, idx)
-            return ops.metrics_mf_mean(ix, cnt, self.gt, list(Ks), mws[len(Ks)], out=out)   # (4,nK) float64
-        if vals.shape[0] == 1 and vals.shape[2] <= _lib_consts.MAX_TOPK and self._local_own is None:
+            if len(Ks) not in self._mean_ws:
+                self._mean_ws[len(Ks)] = ops.metrics_mf_mean_workspace(idx.shape[1], len(Ks), idx.device)
+            return ops.metrics_mf_mean(ix, cnt, self.gt, list(Ks), self._mean_ws[len(Ks)], out=out)   # (4,nK) float64
+        if vals.shape[0] == 1 and vals.shape[2] <= _lib.MAX_TOPK and self._local_own is None:
             # one sorted list per query: the metrics kernel completes short lists with the masked ids itself (-inf fill,
             # batch_test.py:124-134) -- no merge launch
             return ops.colmean(ops.metrics_foldout(idx[0], self.gt, hr_in_ap_slot=True, fill_mask=self.mask), out=out)
         _, ix, _ = ops.topk_merge(vals, idx, self.mask)                                      # -inf fill, batch_test.py:124-134
         return ops.colmean(ops.metrics_foldout(ix, self.gt, hr_in_ap_slot=True), out=out)   # (U,5*max_top) fp32
 
-    def _direct(self, flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, branch=None):
-        vals, idx = self.rank_local(kind, users_tab, user_ids, items_tab, max(Ks), w, wu, c, branch)
+    def _direct(self, flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, branch=None, **launch):
+        vals, idx = self.rank_local(kind, users_tab, user_ids, items_tab, max(Ks), w, wu, c, branch, **launch)
         if sharding.world()[1] > 1:
             lv, li, _ = ops.topk_merge(vals, idx)
             vals, idx = sharding.gather_topk(lv, li)
@@ -326,9 +301,6 @@ class Evaluator(object):
     def _c_scalar(self, c):
         """The evaluator's device copy of c: kernels read it at run time (macr_score_topk c_dev), so the captured
         graph of an evaluation serves every c of a sweep -- only this scalar is rewritten between replays."""
-        if getattr(self, "_c_dev", None) is None:
-            self._c_dev = torch.zeros(1, dtype=torch.float32, device=self.device)
-            self._c_host = None
         if self._c_host != float(c):
             self._c_dev.fill_(float(c))
             self._c_host = float(c)
@@ -345,165 +317,89 @@ class Evaluator(object):
         c = self._c_scalar(c)
         world = sharding.world()[1]
         if (self.optimistic and self.use_graph and world == 1 and self.device.type == "cuda"
-                and self.n_queries <= self.max_queries_per_pass and max(Ks) <= _lib_consts.MAX_TOPK_FUSED):
+                and self.n_queries <= self.max_queries_per_pass and max(Ks) <= _lib.MAX_TOPK_FUSED):
             return self._means_optimistic(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, branch)
         self._last_info = None
-        # (no seeds yet for this K and shard: the first ranking samples, and leaves them)
+        # (no seeds yet for this K and shard: the first ranking samples, and leaves them -- the warm-up run of a capture
+        # creates the seeds: the capture itself must not pick them up)
         seeded = self._seed_feedback() and self.n_queries <= self.max_queries_per_pass and self._has_seeds(max(Ks), items_tab.shape[0], branch)
-        self._seeded_now = seeded        # the warm-up run of a capture creates the seeds: the capture itself must not pick them up
         try:
-            return self._means_launch(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, world, seeded, branch=branch)
+            return self._means_launch(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, world, branch,
+                                      seeded=seeded, filter=self.filter_now)[0]
         finally:
             self._stats_readback(seeded)
 
     def _means_optimistic(self, flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, branch=None):
         """First round only, results in pinned host memory; the rest of the ranking when the first round says so."""
-        if self._stats_evt is not None:           # (a stats copy of the complete path still in flight: not needed any more)
-            self._stats_evt = None
-        seeded = (self.use_seeds and self._seed_skip == 0 and self._has_seeds(max(Ks), items_tab.shape[0], branch))
-        if self.use_seeds and self._seed_skip > 0:
-            self._seed_skip -= 1
+        self._stats_evt = None                    # (a stats copy of the complete path still in flight: not needed any more)
+        seeded, self._policy = eval_policy.seed_first_round(self._policy, self.use_seeds,
+                                                            self._has_seeds(max(Ks), items_tab.shape[0], branch))
         used = self.filter_now
-        try:
-            return self._means_optimistic_run(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, seeded, branch)
-        finally:
-            info = getattr(self, "_last_info", None) or {}
-            if used == "f16":
-                if info.get("exact_fallback") or (not seeded and info.get("query_blocks_relisted")):
-                    self._f16_skip = self._f16_backoff
-                    self._f16_backoff = min(16, 2 * self._f16_backoff)
-                elif not info.get("redone"):
-                    self._f16_backoff = 1
-            else:
-                if self.filter == "f16" and self._f16_skip > 0 and not (used == "f32" and self._bf16_skip > 0):
-                    self._f16_skip -= 1                  # (an evaluation spent in the bf16 tier; fp32 ones count for the bf16 tier's own wait)
-                if used == "bf16":
-                    if info.get("exact_fallback"):
-                        self._bf16_skip = self._bf16_backoff
-                        self._bf16_backoff = min(16, 2 * self._bf16_backoff)
-                    elif not info.get("redone"):
-                        self._bf16_backoff = 1
-                elif self._bf16_skip > 0:
-                    self._bf16_skip -= 1
-            if getattr(self, "_last_info", None) is not None:
-                self._last_info["filter"] = used
 
-    def _means_optimistic_run(self, flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, seeded, branch=None):
-        self._seeded_now = seeded
-        self._topk_mode = "first"
-        try:
-            out = self._means_launch(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, 1, seeded, mode="first", branch=branch)
-            first_entry = self._last_entry
-        finally:
-            self._topk_mode = None
+        def launch(mode, repair_of=None):
+            return self._means_launch(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, 1, branch,
+                                      seeded=seeded, mode=mode, repair_of=repair_of, filter=used)
+        out, entry, ran_complete = launch("first")
         torch.cuda.current_stream().synchronize()
         self._last_seeded = False                 # (nothing for _seed_feedback to read later)
-        relisted = int(self._stats_first[0])
-        self._last_info = {"seeded": bool(seeded), "query_blocks_relisted": relisted, "exact_fallback": 0, "redone": relisted != 0}
-        if self.__dict__.pop("_complete_ran", False):
+        relisted, fallback = self._stats_first.tolist()[0], 0
+        redone = relisted != 0
+        if ran_complete:
             # graph replay was just switched off and the COMPLETE sequence ran in place of the first round: what it relisted and
             # whether it fell back are in its own statistics (the bf16 back-off must see a fallback there too)
-            st = self._stats.tolist()
-            self._last_info.update(query_blocks_relisted=st[0], exact_fallback=st[1])
-            return out.clone()
-        if relisted == 0:
+            relisted, fallback = self._stats.tolist()
+        elif not redone:
             self.fast_stats["fast"] += 1
-            if seeded:
-                self._seed_backoff = 1
-            return out.clone()
-        # a list overflowed or seeds were stale: the repair round (and, behind it, the exact fallback) on the first round's
-        # workspace and outputs -- what the complete call would have launched
-        self.fast_stats["redone"] += 1
-        if seeded and relisted > self._relist_tolerance():
-            self._seed_skip = self._seed_backoff
-            self._seed_backoff = min(16, 2 * self._seed_backoff)
-        if first_entry is None or len(first_entry) < 4:      # (no graph of the first round: it ran as the complete call already)
-            return out.clone()
-        self._topk_mode, self._repair_bufs = "repair", first_entry[3]
-        try:
-            out = self._means_launch(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, 1, seeded, mode="repair", branch=branch)
-        finally:
-            self._topk_mode, self._repair_bufs = None, None
-        torch.cuda.current_stream().synchronize()
-        self._last_info["exact_fallback"] = int(self._stats_first[1])
+        else:
+            # a list overflowed or seeds were stale: the repair round (and, behind it, the exact fallback) on the first round's
+            # workspace and outputs -- what the complete call would have launched
+            self.fast_stats["redone"] += 1
+            out = launch("repair", entry[3])[0]
+            torch.cuda.current_stream().synchronize()
+            fallback = int(self._stats_first[1])
+        self._last_info = {"seeded": seeded, "query_blocks_relisted": relisted, "exact_fallback": fallback, "redone": redone,
+                           "filter": used}
+        self._policy = eval_policy.after_outcome(self._policy, self.filter, used, seeded, relisted, fallback, redone,
+                                                 eval_policy.relist_tolerance(self.n_queries), ran_complete)
         return out.clone()
 
     def last_eval_info(self):
         """What the last evaluation did: {"seeded": its thresholds came from the previous ranking's candidates,
         "query_blocks_relisted": blocks of 256 queries whose lists overflowed / whose seeds were stale, "exact_fallback",
         "redone": the first round did not stand and the complete sequence ran (optimistic mode)}.  Synchronises."""
-        if getattr(self, "_last_info", None) is not None:
+        if self._last_info is not None:
             return dict(self._last_info)
         st = self._stats.tolist()
         return {"seeded": bool(self._last_seeded), "query_blocks_relisted": st[0], "exact_fallback": st[1], "redone": False}
 
-    def _means_launch(self, flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, world, seeded, mode=None, branch=None):
-        self._last_entry = None
-        if not self.use_graph:
-            return self._direct(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, branch)
-        host_out = None
-        if mode:
-            hk = (flavour, Ks)
-            if hk not in self._host_out:
-                shape = (4, len(Ks)) if flavour == "mf" else (5 * max(Ks),)
-                self._host_out[hk] = torch.zeros(shape, dtype=torch.float64).pin_memory()
-            host_out = self._host_out[hk]
-        key = (flavour, mode, self.filter_now, kind, seeded, users_tab.data_ptr(), None if user_ids is None else user_ids.data_ptr(), items_tab.data_ptr(),
-               Ks, None if w is None else w.data_ptr(), None if wu is None else wu.data_ptr(), None if branch is None else branch.data_ptr(),
-               torch.cuda.current_stream().cuda_stream, world)
-        entry = self._graphs.get(key)
-        if entry is None:
+    # ------------------------------------------------------------------ graph cache
+    def _captured(self, key, shape_key, direct, capture, scratch):
+        """A launch sequence the cache has no graph of: warm-up run, capture, keep-alive list -> the new entry
+        (stages, out, keep, first_bufs), or None where graph replay has just been switched off (shape_key given: misses count).
+        capture() -> (stages, out, first_bufs); scratch(): the cached buffers the launches touched."""
+        if shape_key is not None:
             # capturing costs about two evaluations: callers that keep changing the sequence are better off launching directly
             # Misses are counted per evaluation SHAPE (tables, query set, score kind, Ks, stream): one shape legitimately needs up
             # to 8 graphs (first / repair round x candidate filter x seeded or not), so a run that evaluates two query sets and
             # meets a back-off must not lose graph replay.  A caller whose tensors change from call to call shows up as many
             # shapes, or as one shape asking for more graphs than its key space has.
-            shape_key = (flavour, kind) + key[5:]
-            misses = self.__dict__.setdefault("_graph_misses_by_shape", {})
+            misses = self._graph_misses_by_shape
             misses[shape_key] = misses.get(shape_key, 0) + 1
             self._graph_misses += 1
             if misses[shape_key] > 8 or len(misses) > 8:
                 self.use_graph = False
                 self._graphs.clear()
-                if mode == "first":
-                    self._topk_mode = None        # (the complete sequence: its result needs no check)
-                    self._stats_first.zero_()
-                    self._complete_ran = True     # (its own statistics are in self._stats: _means_optimistic_run reads them)
-                return self._direct(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, branch)
-            self._direct(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, branch)     # warm-up: allocations, caches, attributes
-            torch.cuda.synchronize()
-            K = max(Ks)
-            if world == 1:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    vals, idx = self.rank_local(kind, users_tab, user_ids, items_tab, K, w, wu, c, branch)
-                    out = self._finish(flavour, vals, idx, Ks, out=host_out)
-                stages = (g, None, None, None)
-                # what a repair round must continue on: the first round's outputs AND the workspace it was captured with
-                # (the per-device cache is regrown whenever a larger evaluator asks: ops._topk_workspace)
-                first_bufs = (vals, idx, ops._topk_ws_cache.get(items_tab.device))
-            else:
-                # several ranks: the collective stays outside -- one graph up to this shard's merged lists, the
-                # all-gather (RCCL), one graph from the gathered lists to the means
-                ga = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(ga):
-                    vals, idx = self.rank_local(kind, users_tab, user_ids, items_tab, K, w, wu, c, branch)
-                    lv, li, _ = ops.topk_merge(vals, idx)
-                gv, gi = sharding.gather_topk(lv, li)                    # static inputs of the second graph
-                gb = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gb):
-                    out = self._finish(flavour, gv, gi, Ks)
-                stages = (ga, (lv, li), (gv, gi), gb)
-                first_bufs = None
-            # the graphs bake in the addresses of everything they touched: keep the inputs and the cached scratch
-            # (ranking workspace, mask bitmaps) alive for as long as they exist, whatever the caches do later
-            keep = [users_tab, user_ids, items_tab, w, wu, c, branch, ops._topk_ws_cache.get(items_tab.device)]
-            keep.extend(self.__dict__.get("_seeds", {}).values())
-            local = [] if self._local_own is None else [self._mask_local] + list(self._mask_local.__dict__.get("_row_ranges", {}).values())
-            for csr in [self.mask] + list(self.mask.__dict__.get("_row_ranges", {}).values()) + local:
-                keep.extend(csr.__dict__.get("_mask_bits", {}).values())
-            entry = self._graphs[key] = (stages, out, keep, first_bufs)
-        self._last_entry = entry
+                return None
+        direct()                                  # warm-up: allocations, caches, attributes
+        torch.cuda.synchronize()
+        stages, out, first_bufs = capture()
+        # the graphs bake in the addresses of everything they touched: keep the inputs and the cached scratch
+        # (ranking workspace, mask bitmaps) alive for as long as they exist, whatever the caches do later
+        entry = self._graphs[key] = (stages, out, scratch(), first_bufs)
+        return entry
+
+    @staticmethod
+    def _replay(entry):
         (ga, local, gathered, gb), out = entry[0], entry[1]
         ga.replay()
         if gb is not None:
@@ -511,6 +407,63 @@ class Evaluator(object):
             gathered[0].copy_(nv); gathered[1].copy_(ni)
             gb.replay()
         return out
+
+    def _means_launch(self, flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, world, branch=None, repair_of=None, **launch):
+        """-> (means, graph entry or None, the complete sequence ran in place of the first round asked for).
+        launch: what rank_local is told (seeded, mode, filter) -- and, with the tensors, the graph's key."""
+        tensors = (users_tab, user_ids, items_tab, w, wu, c, branch)
+        direct = lambda **kw: self._direct(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c, branch, **kw)
+        if not self.use_graph:
+            return direct(repair_of=repair_of, **launch), None, False
+        mode = launch.get("mode")
+        host_out = None
+        if mode:
+            hk = (flavour, Ks)
+            if hk not in self._host_out:
+                shape = (4, len(Ks)) if flavour == "mf" else (5 * max(Ks),)
+                self._host_out[hk] = torch.zeros(shape, dtype=torch.float64).pin_memory()
+            host_out = self._host_out[hk]
+        shape_key = (flavour, kind, Ks, torch.cuda.current_stream().cuda_stream, world) + _ptrs(users_tab, user_ids, items_tab, w, wu, branch)
+        key = shape_key + tuple(sorted(launch.items()))
+        entry = self._graphs.get(key)
+        if entry is None:
+            K = max(Ks)
+
+            def capture():
+                if world == 1:
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        vals, idx = self.rank_local(kind, users_tab, user_ids, items_tab, K, w, wu, c, branch, repair_of=repair_of, **launch)
+                        out = self._finish(flavour, vals, idx, Ks, out=host_out)
+                    # what a repair round must continue on: the first round's outputs AND the workspace it was captured with
+                    # (the per-device cache is regrown whenever a larger evaluator asks: ops._topk_workspace)
+                    return (g, None, None, None), out, (vals, idx, ops._topk_ws_cache.get(items_tab.device))
+                # several ranks: the collective stays outside -- one graph up to this shard's merged lists, the
+                # all-gather (RCCL), one graph from the gathered lists to the means
+                ga = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(ga):
+                    vals, idx = self.rank_local(kind, users_tab, user_ids, items_tab, K, w, wu, c, branch, **launch)
+                    lv, li, _ = ops.topk_merge(vals, idx)
+                gv, gi = sharding.gather_topk(lv, li)                    # static inputs of the second graph
+                gb = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gb):
+                    out = self._finish(flavour, gv, gi, Ks)
+                return (ga, (lv, li), (gv, gi), gb), out, None
+
+            def scratch():
+                keep = list(tensors) + [ops._topk_ws_cache.get(items_tab.device)] + list(self._seeds.values())
+                local = [] if self._local_own is None else [self._mask_local] + list(self._mask_local.__dict__.get("_row_ranges", {}).values())
+                for csr in [self.mask] + list(self.mask.__dict__.get("_row_ranges", {}).values()) + local:
+                    keep.extend(csr.__dict__.get("_mask_bits", {}).values())
+                return keep
+            entry = self._captured(key, shape_key, lambda: direct(repair_of=repair_of, **launch), capture, scratch)
+            if entry is None:                     # graph replay switched off
+                if mode != "first":
+                    return direct(repair_of=repair_of, **launch), None, False
+                # the complete sequence: its result needs no check, and its own statistics are in self._stats
+                self._stats_first.zero_()
+                return direct(**dict(launch, mode=None)), None, True
+        return self._replay(entry), entry, False
 
     # ------------------------------------------------------------------ c sweep (tuners)
     def _sweep_direct(self, flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c_dev, branch=None):
@@ -524,7 +477,6 @@ class Evaluator(object):
         """Column means of the per-user metrics for every c of `cs`, (len(cs), ...).  On one GPU the values go through
         the shared-listing-pass kernel in groups of up to four (one captured graph per group size, the group's values
         in a device array the kernels read at run time); item-sharded runs evaluate c by c."""
-        from . import _lib
         cs = [float(c) for c in cs]
         # The shared-listing-pass kernels follow the candidate filter (k_score_stream_bs under "bf16": 0.31 ms per value
         # on the Gowalla shape against 0.43 one evaluation at a time, tools/bench_sweep.py).  MACR_SWEEP_ONE_BY_ONE=1
@@ -537,29 +489,26 @@ class Evaluator(object):
         for a in range(0, len(cs), _lib.MAX_SWEEP):
             chunk = cs[a:a + _lib.MAX_SWEEP]
             n = len(chunk)
-            bufs = self.__dict__.setdefault("_c_sweep", {})
-            if n not in bufs:
-                bufs[n] = torch.zeros(n, dtype=torch.float32, device=self.device)
-            c_dev = bufs[n]
+            if n not in self._c_sweep:
+                self._c_sweep[n] = torch.zeros(n, dtype=torch.float32, device=self.device)
+            c_dev = self._c_sweep[n]
             c_dev.copy_(torch.tensor(chunk, dtype=torch.float32), non_blocking=False)
+            direct = lambda: self._sweep_direct(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c_dev, branch)
             if not self.use_graph:
-                outs.append(self._sweep_direct(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c_dev, branch).clone())
+                outs.append(direct().clone())
                 continue
-            key = ("sweep", n, flavour, self.filter, kind, users_tab.data_ptr(), None if user_ids is None else user_ids.data_ptr(),
-                   items_tab.data_ptr(), Ks, w.data_ptr(), None if wu is None else wu.data_ptr(), None if branch is None else branch.data_ptr(),
-                   torch.cuda.current_stream().cuda_stream)
+            key = ("sweep", n, flavour, self.filter, kind, Ks, torch.cuda.current_stream().cuda_stream) + _ptrs(users_tab, user_ids, items_tab, w, wu, branch)
             entry = self._graphs.get(key)
             if entry is None:
-                self._sweep_direct(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c_dev, branch)       # warm-up
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    out = self._sweep_direct(flavour, kind, users_tab, user_ids, items_tab, Ks, w, wu, c_dev, branch)
-                keep = [users_tab, user_ids, items_tab, w, wu, c_dev, branch, ops._sweep_ws_cache.get(items_tab.device)]
-                keep.extend(self.mask.__dict__.get("_mask_bits", {}).values())
-                entry = self._graphs[key] = ((g, None, None, None), out, keep)
-            entry[0][0].replay()
-            outs.append(entry[1].clone())
+                def capture():
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        out = direct()
+                    return (g, None, None, None), out, None
+                scratch = lambda: ([users_tab, user_ids, items_tab, w, wu, c_dev, branch, ops._sweep_ws_cache.get(items_tab.device)]
+                                   + list(self.mask.__dict__.get("_mask_bits", {}).values()))
+                entry = self._captured(key, None, direct, capture, scratch)       # (a sweep's graphs are no misses)
+            outs.append(self._replay(entry).clone())
         return torch.cat(outs)
 
     def test_mf_sweep(self, kind, users_tab, user_ids, items_tab, Ks, w, wu, cs, branch=None):
@@ -586,6 +535,16 @@ class Evaluator(object):
         final = self._means("lgcn", kind, users_tab, user_ids, items_tab, tuple(Ks), w, wu, c, branch).cpu().numpy()
         final = final.reshape(5, max_top)[:, top_show - 1]
         return {'hr': final[2].copy(), 'recall': final[1].copy(), 'ndcg': final[3].copy()}
+
+
+def _policy_field(name):
+    """`_seed_skip` ... `_bf16_backoff`: the policy's counters, readable and writable (bench.py resets `_seed_skip`)"""
+    return property(lambda self: getattr(self._policy, name),
+                    lambda self, value: setattr(self, "_policy", self._policy._replace(**{name: value})))
+
+
+for _name in eval_policy.State._fields:
+    setattr(Evaluator, "_" + _name, _policy_field(_name))
 
 
 def eval_score_matrix_foldout(score_matrix, test_items, top_k=20, thread_num=None):

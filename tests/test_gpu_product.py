@@ -1008,3 +1008,25 @@ def test_evaluator_seeds_follow_the_model_and_back_off_when_it_jumps(ops, eval_f
     # graphs: the first round seeded and sampled, and the complete sampled sequence the stale evaluation fell back to
     assert len(ev._graphs) == (3 if ev.optimistic else 2)
     assert ev.fast_stats == ({"fast": 8, "redone": 1} if ev.optimistic else {"fast": 0, "redone": 0})
+
+
+def _eval_policy_recorder():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_golden_eval_policy", os.path.join(GOLD, "make_golden_eval_policy.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.mark.parametrize("filt", ["f32", "f16"])
+@pytest.mark.parametrize("kind_name", ["SCORE_NORMAL", "SCORE_RUBI_BOTH"])
+@pytest.mark.parametrize("flavour", ["mf", "lgcn"])
+def test_evaluation_launches_the_recorded_kernels(ops, flavour, kind_name, filt):
+    """The launches of an evaluation, by name and in order, are those recorded before the evaluator was split into policy,
+    launch arguments and graph cache (tests/golden/make_golden_eval_policy.py --gpu; U=513, N=20011, d=128, a shape that
+    ranks with thresholds): an unseeded evaluation, then a seeded one, launched directly."""
+    import json
+    with open(os.path.join(GOLD, "G14_eval_policy.json")) as f:
+        want = json.load(f)["kernel_names"]["%s/%s/%s" % (flavour, kind_name, filt)]
+    got = _eval_policy_recorder().kernel_names(flavour, kind_name, filt)
+    assert got == want
