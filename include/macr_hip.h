@@ -348,6 +348,39 @@ int macr_sample_triples_many(uint64_t seed, uint64_t step0, int n_steps, int B, 
                              const int32_t *excl_ptr, const int32_t *excl_idx, int32_t *out, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Host-side sampler of the REFERENCE'S OWN random stream (additive, abi 16): the batches Data.sample of
+ * macr_mf/load_data.py:543-566 and Data.sample / Data.sample_test of macr_lightgcn/utility/load_data.py:174-212, :214-254
+ * draw from Python's `random` and numpy.random, bit for bit, and the generator states those loops leave behind
+ * (macr_amd/csrc/ref_sampler_core.hpp spells the stream out).  HOST POINTERS ONLY, no stream argument, no device work:
+ * MT19937 behind rejection loops is one sequential chain.  No allocation and no global state: scratch is the caller's.
+ *   kind        MACR_REFSTREAM_MF: users, positives and negatives from the Python generator;
+ *               MACR_REFSTREAM_LGCN: users from the Python generator, items from the NumPy generator
+ *   n_users     rows of both CSRs; B <= n_users draws B distinct users (random.sample), B > n_users B independent ones
+ *               (random.choice), exactly as the reference decides
+ *   pop         int32[n_pop] ids in [0, n_users): range(n_users) (MF), exist_users in file order (LightGCN), the keys of
+ *               test_set in insertion order (sample_test)
+ *   pos_ptr / pos_idx    int32[n_users+1] / items: the lists the positives come from, IN LIST ORDER (a draw is an index
+ *               into the list).  An empty list gives item 0 without a draw (MF) or MACR_E_INVALID (LightGCN: the
+ *               reference raises)
+ *   excl_ptr / excl_idx  the items a negative must avoid, ascending without duplicates: the train lists, or test and
+ *               train lists together for sample_test
+ *   py_key / py_pos      uint32[624] + position 0..624 = random.getstate()[1]; in: where to continue, out: where the
+ *   np_key / np_pos      Python loop would stand after these batches.  Same for np.random.get_state()[1:3]
+ *   out         int32[n_batches][3][B] = users | pos_items | neg_items per batch
+ *   workspace   at least the bytes the query below returns for n_pop
+ * Refused with MACR_E_INVALID before any draw (states and out untouched; the reference would raise or spin for ever): a
+ * null pointer, B <= 0, a position outside 0..624, B <= n_users with B > n_pop, a population id outside the CSRs, an
+ * exclusion list that covers all n_items.  Any failure leaves both states as they came in.
+ * -------------------------------------------------------------------------*/
+#define MACR_REFSTREAM_MF   0
+#define MACR_REFSTREAM_LGCN 1
+size_t macr_ref_sample_workspace_bytes(int n_pop);
+int macr_ref_sample_batches(int kind, int n_batches, int B, int n_users, const int32_t *pop, int n_pop,
+                            const int32_t *pos_ptr, const int32_t *pos_idx, const int32_t *excl_ptr,
+                            const int32_t *excl_idx, int n_items, uint32_t *py_key, int *py_pos, uint32_t *np_key,
+                            int *np_pos, int32_t *out, void *workspace, size_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------
  * SpMM plan (host side, built once per graph -- the adjacency never changes).
  * Interaction graphs have hub rows (items with 10^4..10^5 neighbours); the plan
  * cuts rows longer than 512 non-zeros into work items of 512 so that no single

@@ -19,6 +19,7 @@ MAX_TOPK_FUSED = 32
 MAX_SWEEP = 4
 ABI_VERSION = 16
 LAZY_STATE_BYTES, LAZY_MAX_PERIOD = 1040, 64
+REFSTREAM_MF, REFSTREAM_LGCN = 0, 1
 
 
 def is_pair_loss(kind):
@@ -77,6 +78,9 @@ SIGNATURES = {
     "macr_lazy_flush": (_i, [_i, _ll, _ll] + [_p] * 6 + [ctypes.POINTER(Hyper), ctypes.POINTER(LazyAdam), _p]),
     "macr_sample_triples": (_i, [ctypes.c_uint64, ctypes.c_uint64, _i, _i, _p, _i, _p, _p, _p, _p]),
     "macr_sample_triples_many": (_i, [ctypes.c_uint64, ctypes.c_uint64, _i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p]),
+    "macr_ref_sample_workspace_bytes": (_z, [_i]),
+    "macr_ref_sample_batches": (_i, [_i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _i, _p, ctypes.POINTER(ctypes.c_int), _p,
+                                     ctypes.POINTER(ctypes.c_int), _p, _p, _z]),
     "macr_spmm_plan_bytes": (_z, [_i, _p, _p, _p]),
     "macr_spmm_plan_build": (_i, [_i, _p, _p, _p, _p, _z]),
     "macr_lgcn_work_floats": (_z, [_i, _i, _p]),

@@ -1,8 +1,8 @@
 """Device-side training sampler (macr_sample_triples) -- `--sampler device` of the CLIs.
 
-The default `--sampler reference` keeps the reference's python `random` / numpy streams (golden G2/G3)
-and is host-bound at ~1 M triples/s; this one draws every batch on the GPU from a counter-based
-generator keyed by (seed, step): same distribution, different stream."""
+The default `--sampler reference` keeps the reference's python `random` / numpy streams (golden G2/G3;
+host_sampler.py draws them in native host code, one sequential chain); this one draws every batch on the
+GPU from a counter-based generator keyed by (seed, step): same distribution, different stream."""
 import ctypes
 
 import torch

@@ -6,9 +6,10 @@
 
 Same flags, log line formats, early stopping and weight-file naming as the reference
 (LightGCN.py:649-904).  The propagation (SpMM), the training step and the evaluator run on the HIP
-kernels; the sampler is the reference's host sampler (python `random` + numpy.random streams),
-overlapped with the device step because kernel launches are asynchronous (the reference needs a
-helper thread for that, :567-647).  The per-log-interval "test loss" pass (:799-819) runs as
+kernels; the sampler draws the reference's host stream (python `random` + numpy.random) in native
+host code, one pass at a time (--sampler reference, macr_amd/host_sampler.py; --sampler python keeps
+the reference's loop, overlapped with the device step because kernel launches are asynchronous -- the
+reference needs a helper thread for that, :567-647).  The per-log-interval "test loss" pass (:799-819) runs as
 loss-only steps (MACR_STEP_LOSS_ONLY) on sample_test() batches, so the host RNG streams stay aligned
 with the reference for a whole run.  Differences: TensorBoard graph dumps are dropped; checkpoints are
 torch files (same directory and file naming), which --pretrain 1 and the additive --resume 1 read back;
@@ -66,7 +67,11 @@ def train_epoch(model, kind, n_batch, loss_log, device_sampler=None, test_loss=F
     sampler's batches -- `--sampler device` builds one over the test lists).
     RNG consumption with the host sampler: the reference fetches one batch ahead (:762-764 / :799-801, then one
     `sample_thread` per iteration :767 / :804), so a pass draws n_batch + 1 batches and throws the last one away; the
-    extra draw below keeps the python `random` / numpy streams -- and so every later epoch's batches -- the same."""
+    extra draw below keeps the python `random` / numpy streams -- and so every later epoch's batches -- the same.  A
+    host_sampler.ReferenceStreamSampler (--sampler reference) draws that very stream natively: its pass is the n_batch + 1
+    batches, the last one never handed out."""
+    if hasattr(device_sampler, "begin_pass"):
+        device_sampler.begin_pass(n_batch + 1)
     for idx in range(n_batch):
         if test_loss and device_sampler is not None:
             batch = device_sampler.sample()
@@ -188,9 +193,15 @@ def main(sweep=False):
         test_sampler = DeviceSampler({u: sorted(data_generator.test_set[u]) for u in test_users}, data_generator.n_users,
                                      data_generator.n_items, args.batch_size, model.device, seed=seed + 1, pool=test_users,
                                      exclude=both)
-    elif args.sampler != "reference":
-        raise SystemExit("--sampler must be reference or device")
-    if device_sampler is not None and start_epoch > 1:
+    elif args.sampler == "reference":
+        # the same batches and the same `random` / numpy states as sample() / sample_test() leave, drawn in native host code
+        from macr_amd.host_sampler import ReferenceStreamSampler
+        device_sampler = ReferenceStreamSampler.for_lgcn(data_generator, device=model.device, batch_size=args.batch_size)
+        test_sampler = ReferenceStreamSampler.for_lgcn(data_generator, test=True, device=model.device,
+                                                       batch_size=args.batch_size)
+    elif args.sampler != "python":
+        raise SystemExit("--sampler must be reference, python or device")
+    if args.sampler == "device" and start_epoch > 1:
         # the batch of step k is a function of (seed, k): continue the sequences instead of replaying epoch 1's batches
         device_sampler.step = resumed['sampler_step'] if resumed else (start_epoch - 1) * n_batch
         test_sampler.step = resumed['test_sampler_step'] if resumed else ((start_epoch - 1) // args.log_interval) * n_batch
@@ -257,8 +268,8 @@ def main(sweep=False):
             train_state.save(weights_save_path + '/train_state_{}-{}.json'.format(args.saveID, epoch),
                              {'bests': [float(cur_best_pre_0), int(stopping_step), int(best_epoch), float(best_hr_norm),
                                         int(best_c_epoch), float(best_c_hr)],
-                              'sampler_step': int(device_sampler.step) if device_sampler is not None else 0,
-                              'test_sampler_step': int(test_sampler.step) if test_sampler is not None else 0})
+                              'sampler_step': int(getattr(device_sampler, 'step', 0)),
+                              'test_sampler_step': int(getattr(test_sampler, 'step', 0))})
             print('save the weights in path: ', weights_save_path)
         if should_stop and args.early_stop == 1:
             if main_rank:

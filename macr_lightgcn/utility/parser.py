@@ -47,7 +47,8 @@ _FLAGS = [
     ("out", int, 0, "(compat)"),
     ("seed", int, 12345, "[new] seed of python/numpy/torch RNGs (the reference hard-codes 12345)"),
     ("resume", int, 0, "[new] 1: load the newest checkpoint of this run's checkpoint directory and continue training"),
-    ("sampler", str, "reference", "[new] reference: the reference's random/numpy streams (host); device: GPU sampler"),
+    ("sampler", str, "reference", "[new] reference: the reference's random/numpy streams, drawn natively (host); "
+                                  "python: the same streams by the reference's loop; device: GPU sampler, other streams"),
 ]
 
 

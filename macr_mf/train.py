@@ -99,9 +99,12 @@ def _ckpt_dir():
 
 
 def train_epoch(model, kind, n_batch, loss_log, device_sampler=None):
-    """n_batch = n_train // batch_size + 1 steps (train.py:467-470).  --sampler reference follows the
-    reference's python `random` stream (host-bound); --sampler device draws the batches on the GPU.
-    Per-step losses stay on the device and come back once per epoch."""
+    """n_batch = n_train // batch_size + 1 steps (train.py:467-470).  Without a sampler object the batches come from
+    data.sample(), the reference's python `random` loop (host-bound; --sampler python); --sampler reference hands in a
+    host_sampler.ReferenceStreamSampler, which draws the same stream natively, one pass of n_batch batches at a time;
+    --sampler device draws other batches on the GPU.  Per-step losses stay on the device and come back once per epoch."""
+    if hasattr(device_sampler, "begin_pass"):
+        device_sampler.begin_pass(n_batch)
     for idx in range(n_batch):
         if device_sampler is not None:
             batch = device_sampler.sample()
@@ -217,9 +220,13 @@ def main(sweep=False):
         from macr_amd.sampler import DeviceSampler
         device_sampler = DeviceSampler(data.train_user_list, data.n_users, data.n_items, args.batch_size,
                                        model.device, seed=seed)
-    elif args.sampler != "reference":
-        raise SystemExit("--sampler must be reference or device")
-    if device_sampler is not None and start_epoch:
+    elif args.sampler == "reference":
+        # the same batches and the same `random` / numpy states as data.sample() leaves, drawn in native host code
+        from macr_amd.host_sampler import ReferenceStreamSampler
+        device_sampler = ReferenceStreamSampler.for_mf(data, device=model.device, batch_size=args.batch_size)
+    elif args.sampler != "python":
+        raise SystemExit("--sampler must be reference, python or device")
+    if args.sampler == "device" and start_epoch:
         # the batch of step k is a function of (seed, k): continue the sequence instead of replaying epoch 0's batches
         device_sampler.step = resumed['sampler_step'] if resumed else start_epoch * n_batch
     # (the reference rebuilds this list at every evaluation, train.py:505-516; one object per run keeps test()'s evaluator
@@ -281,7 +288,7 @@ def main(sweep=False):
             train_state.save(_ckpt_dir() + '{}_train_state.json'.format(epoch),
                              {'config': {k: (v.item() if hasattr(v, 'item') else v) for k, v in config.items() if k.startswith('best_')},
                               'stopping_step': int(stopping_step),
-                              'sampler_step': int(device_sampler.step) if device_sampler is not None else 0})
+                              'sampler_step': int(getattr(device_sampler, 'step', 0))})
         if should_stop and args.early_stop == 1:
             say("{} dataset best epoch{}: hr:{} ndcg:{} recall:{} precision:{}".format(
                 args.dataset, config['best_epoch'], config['best_hr'], config['best_ndcg'], config['best_recall'],
