@@ -687,7 +687,8 @@ struct StreamHeader {             // all int32; follows the row plan at PlanHead
 constexpr int32_t kStreamMagic = 0x4d535452;   // "MSTR"
 constexpr int kStreamHubDefault = 512;   // rows with more neighbours are cut into pieces (MACR_SPMM_HUB at plan time)
 constexpr int kStreamPiece = 256; // entries per piece (255 neighbours + its end marker)
-// layout after the header: chunk_desc[n_chunks] = {first sub-batch (32 entries), end, first empty row | count << 24, slot or -1}, empties[n_empty],
+// layout after the header: chunk_desc[n_chunks] = {first sub-batch (32 entries), end, first empty row | count << 24, slot or -1}
+// (behind the chunks there may be descriptors with first = end: no entries, only a share of the empties), empties[n_empty],
 // slot_group[n_slots], group_slot0[n_groups+1], group_split[n_groups], split_group0[n_split+1],
 // split_row[n_split], then (64-byte aligned) pcw[n_entries + 128] = {column | bit 31 for an end marker, weight bits (marker: 0 row, 1 piece)}
 struct StreamView {
@@ -1096,9 +1097,28 @@ int launch_propagate(int N, int d, int n_layers, const int32_t *rowptr, const in
     return MACR_OK;
 }
 
-static int plan_chunk() {
-    static const int c = getenv("MACR_SPMM_CHUNK") && atoi(getenv("MACR_SPMM_CHUNK")) >= 64 ? atoi(getenv("MACR_SPMM_CHUNK")) : kChunk;
-    return c;
+// The plan-time knobs (kernel-development switches in the environment), read ONCE PER PLAN BUILD -- both sections of a plan
+// see the same values, and two plans built in one process may differ.  Nothing at launch time depends on them: the
+// launcher takes `chunk` from the plan's header.  (MACR_SPMM_STREAM, read in build_whole_plan, is plan-time as well;
+// MACR_SPMM_STREAM_FUSED, MACR_SPMM_RECORDS and MACR_LGCN_BWD1_DENSE sit on the step's hot path and stay latched per process.)
+struct PlanKnobs {
+    int chunk;                    // MACR_SPMM_CHUNK (>= 64): non-zeros per piece of the row plan
+    bool octants;                 // MACR_SPMM_OCTANTS (0: off): hub pieces cut at the source ranges and placed XCD by XCD
+    int stream_hub;               // MACR_SPMM_HUB (>= 32): stream rows with more neighbours are cut into pieces
+    int stream_target;            // MACR_SPMM_T (>= 32): entries per chunk of the stream
+};
+static PlanKnobs read_plan_knobs() {
+    auto at_least = [](const char *name, int lo, int dflt) {
+        const char *e = getenv(name);
+        return e && atoi(e) >= lo ? atoi(e) : dflt;
+    };
+    PlanKnobs k;
+    k.chunk = at_least("MACR_SPMM_CHUNK", 64, kChunk);
+    const char *o = getenv("MACR_SPMM_OCTANTS");
+    k.octants = !(o && atoi(o) == 0);
+    k.stream_hub = at_least("MACR_SPMM_HUB", 32, kStreamHubDefault);
+    k.stream_target = at_least("MACR_SPMM_T", 32, 256);
+    return k;
 }
 
 // Eight ranges of source rows of equal entry mass over the rows longer than `hub` (see build_stream: XCD affinity).
@@ -1116,10 +1136,6 @@ static void source_octants(int N, const int32_t *rowptr, const int32_t *col, int
     }
     for (; x <= kNumXcd; ++x) bound[x] = N;
     bound[kNumXcd] = N;
-}
-static bool plan_octants() {
-    static const bool on = !(getenv("MACR_SPMM_OCTANTS") && atoi(getenv("MACR_SPMM_OCTANTS")) == 0);
-    return on;
 }
 // `queues[x]`: what should run on XCD x (block j of a launch lands on XCD j % 8 and takes four consecutive work items);
 // `free_items`: what may run anywhere.  Returns the launch order: block j = four items of queue j % 8, the shortest queue
@@ -1151,12 +1167,13 @@ static std::vector<int32_t> xcd_order(std::vector<int32_t> (&q)[kNumXcd], const 
     return order;
 }
 
-static void build_plan(int N, const int32_t *rowptr, const int32_t *col, const float *val, std::vector<int32_t> &out) {
+static void build_plan(int N, const int32_t *rowptr, const int32_t *col, const float *val, const PlanKnobs &knobs,
+                       std::vector<int32_t> &out) {
     struct Item { int32_t row, beg, end, slot; };
     std::vector<Item> items;
     std::vector<int32_t> slot_group, group_slot0, group_split, split_group0, split_row, piece_xcd;
-    const int chunk = plan_chunk();
-    const bool octants = col && plan_octants();
+    const int chunk = knobs.chunk;
+    const bool octants = col && knobs.octants;
     int32_t bound[kNumXcd + 1] = {};
     if (octants) source_octants(N, rowptr, col, chunk, bound);
     auto octant_of = [&](int32_t c) { int x = 0; while (x + 1 < kNumXcd && c >= bound[x + 1]) ++x; return x; };
@@ -1255,19 +1272,12 @@ static void build_plan(int N, const int32_t *rowptr, const int32_t *col, const f
 
 
 // The entry stream of k_spmm_stream (see there).  Appends the stream section (64-byte aligned) to `out`, the row plan.
-static int stream_target() {
-    static const int t = getenv("MACR_SPMM_T") && atoi(getenv("MACR_SPMM_T")) >= 32 ? atoi(getenv("MACR_SPMM_T")) : 256;
-    return t;
-}
-static int stream_hub() {
-    static const int t = getenv("MACR_SPMM_HUB") && atoi(getenv("MACR_SPMM_HUB")) >= 32 ? atoi(getenv("MACR_SPMM_HUB")) : kStreamHubDefault;
-    return t;
-}
-static void build_stream(int N, const int32_t *rowptr, const int32_t *col, const float *val, std::vector<int32_t> &out) {
-    const int kStreamHub = stream_hub();
+static void build_stream(int N, const int32_t *rowptr, const int32_t *col, const float *val, const PlanKnobs &knobs,
+                         std::vector<int32_t> &out) {
+    const int kStreamHub = knobs.stream_hub;
     std::vector<int32_t> pc, prow, chunk_slot, empties, slot_group, group_slot0, group_split, split_group0, split_row;
     std::vector<float> pv;
-    const int T = stream_target();
+    const int T = knobs.stream_target;
     pc.reserve((size_t)rowptr[N] + 8 * (size_t)N); pv.reserve(pc.capacity());
     // an entry; rows end only at the last entry of a group of 8 (prow: one int per group)
     auto emit = [&](int32_t c, float w) {
@@ -1299,7 +1309,7 @@ static void build_stream(int N, const int32_t *rowptr, const int32_t *col, const
     // chunk order below puts the pieces of range x into blocks that land on XCD x: that L2 then serves one eighth of the
     // source rows (~1 MB of an 8 MB user table) instead of all of them.  Placement is the driver's habit, not a promise:
     // results do not depend on it, only the L2 hit rate does.  MACR_SPMM_OCTANTS=0 keeps stream order.
-    const bool octants = plan_octants();
+    const bool octants = knobs.octants;
     int32_t bound[kNumXcd + 1];
     source_octants(N, rowptr, col, kStreamHub, bound);
     std::vector<int32_t> chunk_xcd;                               // per chunk: the XCD its block should land on, -1 any
@@ -1343,6 +1353,9 @@ static void build_stream(int N, const int32_t *rowptr, const int32_t *col, const
         }
     }
     close_chunk(-1);
+    // a descriptor names its share of the empties as {first index: 24 bits, count: 8 bits}; a graph with 2^24 rows without
+    // neighbours gets no stream (the row kernel runs its dense layers)
+    if (empties.size() >= ((size_t)1 << 24)) return;
     group_slot0.push_back(n_slots);
     split_group0.push_back((int32_t)group_split.size());
     const int n_chunks = (int)chunk_start.size();
@@ -1358,11 +1371,15 @@ static void build_stream(int N, const int32_t *rowptr, const int32_t *col, const
         for (int k = 0; k < n_chunks; ++k) (chunk_xcd[k] >= 0 ? q[chunk_xcd[k]] : free_chunks).push_back(k);
         order = xcd_order(q, free_chunks);
     }
-    std::vector<int32_t> chunk_empty(n_chunks + 1);
-    for (int k = 0; k <= n_chunks; ++k) chunk_empty[k] = (int32_t)((long long)empties.size() * k / (n_chunks ? n_chunks : 1));
-    if (n_chunks == 0) chunk_empty[0] = 0;
+    // the empties are shared out evenly, at most 255 to a descriptor (the count has 8 bits): where the chunks are too few for
+    // that -- more than 255 rows without neighbours per chunk -- descriptors WITHOUT entries (first sub-batch = end) follow
+    // the chunks and take the rest; the kernel walks no round for them
+    const int n_desc = std::max(n_chunks, (int)((empties.size() + 254) / 255));
+    std::vector<int32_t> chunk_empty(n_desc + 1);
+    for (int k = 0; k <= n_desc; ++k) chunk_empty[k] = (int32_t)((long long)empties.size() * k / (n_desc ? n_desc : 1));
+    if (n_desc == 0) chunk_empty[0] = 0;
     StreamHeader h = {};
-    h.magic = kStreamMagic; h.n_chunks = n_chunks; h.n_sb = (int32_t)(pc.size() / 32); h.n_empty = (int32_t)empties.size();
+    h.magic = kStreamMagic; h.n_chunks = n_desc; h.n_sb = (int32_t)(pc.size() / 32); h.n_empty = (int32_t)empties.size();
     h.n_slots = n_slots; h.n_groups = (int32_t)group_split.size(); h.n_split = (int32_t)split_row.size();
     h.n_entries = (int32_t)pc.size();
     while ((out.size() * 4) % 64) out.push_back(0);
@@ -1372,7 +1389,11 @@ static void build_stream(int N, const int32_t *rowptr, const int32_t *col, const
     for (int pos = 0; pos < n_chunks; ++pos) {
         const int k = order[pos];
         const int32_t ne = chunk_empty[pos + 1] - chunk_empty[pos];
-        out.push_back(sbv[k]); out.push_back(sbv[k + 1]); out.push_back(chunk_empty[pos] | (ne << 24)); out.push_back(chunk_slot[k]);
+        out.push_back(sbv[k]); out.push_back(sbv[k + 1]); out.push_back(chunk_empty[pos] | (int32_t)((uint32_t)ne << 24)); out.push_back(chunk_slot[k]);
+    }
+    for (int pos = n_chunks; pos < n_desc; ++pos) {
+        const int32_t ne = chunk_empty[pos + 1] - chunk_empty[pos];
+        out.push_back(sbv[n_chunks]); out.push_back(sbv[n_chunks]); out.push_back(chunk_empty[pos] | (int32_t)((uint32_t)ne << 24)); out.push_back(-1);
     }
     out.insert(out.end(), empties.begin(), empties.end());
     out.insert(out.end(), slot_group.begin(), slot_group.end());
@@ -1397,11 +1418,12 @@ using namespace macr;
 
 // ---- plan (host) ----------------------------------------------------------------
 static void build_whole_plan(int N, const int32_t *rowptr, const int32_t *col, const float *val, std::vector<int32_t> &v) {
-    build_plan(N, rowptr, col, val, v);
+    const PlanKnobs knobs = read_plan_knobs();                  // once per plan: both sections see the same values
+    build_plan(N, rowptr, col, val, knobs, v);
     // The entry stream is an option (MACR_SPMM_STREAM=1 at plan time): with the XCD-affine piece order both kernels sit at
     // the same level (stand-alone dense layer at the Yelp2018 shape: row kernel 42.7 us, stream kernel 46.3; LightGCN step
     // 205-209 us either way), and the row kernel needs no second copy of the matrix.
-    if (col && val && getenv("MACR_SPMM_STREAM") && atoi(getenv("MACR_SPMM_STREAM")) != 0) build_stream(N, rowptr, col, val, v);
+    if (col && val && getenv("MACR_SPMM_STREAM") && atoi(getenv("MACR_SPMM_STREAM")) != 0) build_stream(N, rowptr, col, val, knobs, v);
 }
 
 extern "C" size_t macr_spmm_plan_bytes(int N, const int32_t *rowptr_host, const int32_t *col_host, const float *val_host) {

@@ -556,6 +556,15 @@ def test_lgcn_propagate_entry_stream_and_piece_orders(ops, d, octants, monkeypat
         adj = ops.CSR.from_scipy(A, "cuda")
         assert adj.plan_host[2] >= 5                      # header: n_split
         assert (adj.plan_host[7] > 0) == (stream == "1")  # header: offset of the stream section
+        # the parametrisation took effect (the knob is read per plan build): without octants the pieces -- the first n_slots
+        # items -- are launched in slot order and are no more than with the cuts at the source ranges; the two plans differ
+        monkeypatch.setenv("MACR_SPMM_OCTANTS", "0" if octants == "1" else "1")
+        other = ops.CSR.from_scipy(A, "cuda").plan_host
+        monkeypatch.setenv("MACR_SPMM_OCTANTS", octants)
+        on, off = (adj.plan_host, other) if octants == "1" else (other, adj.plan_host)
+        n_on, n_off = int(on[3]), int(off[3])              # header: n_slots
+        assert n_on >= n_off > 0 and not (len(on) == len(off) and np.array_equal(on, off))
+        assert np.array_equal(off[16:16 + 4 * n_off].reshape(-1, 4)[:, 3], np.arange(n_off))
         for L in (1, 2, 3):
             want = oracle.lgcn_propagate(A.indptr, A.indices, A.data, E0, L)
             ops.timing_begin()
