@@ -762,6 +762,34 @@ int macr_metrics_mf_mean(int U, int Kmax, const int32_t *rankings, const int32_t
                          const int32_t *Ks /*host*/, int nK, double *per_user, double *mean,
                          void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Per-item counts of a ranking (additive, abi 16): the device half of the item_acc_list both test() functions of the
+ * reference build in a Python double loop (macr_mf/train.py:261-277 with k = 5; macr_lightgcn/utility/batch_test.py:94-115
+ * with k = 20): item_acc_list[i] = hit_cnt[i] additions of 1 / (test interactions of i).
+ *   rankings  (dev) int32[U*K]: per query the ranked ids outside its train list, best first, -1 in unused slots (what
+ *             macr_score_topk / macr_topk_merge leave without the -inf fill); only the first k of a row are read
+ *   gt_ptr / gt_idx (dev) the ground truth as CSR, ascending per query, as macr_metrics_mf takes it
+ *   group_of  (dev, may be NULL) int32[n_items]: the popularity group of every item, 0 .. n_groups-1 (an item with
+ *             another value is in no group's sum); n_groups in [1, 64] when given
+ *   rec_cnt   (dev) int32[n_items] <- users whose first k ranked ids contain the item (ids < 0 are skipped, and so is an id
+ *             >= n_items: nothing is written outside the arrays)
+ *   hit_cnt   (dev) int32[n_items] <- the same count over the users whose ground truth contains the item
+ *   group_out (dev, may be NULL) long long[n_groups*2] <- per group {sum of rec_cnt, sum of hit_cnt}; written when group_of
+ *             and group_out are both given
+ *   workspace (dev) >= macr_item_counts_workspace_bytes(U, K, n_items) bytes, 8-byte aligned: a few copies of a packed 64-bit
+ *             {rec, hit} counter per item.  Contents need not be initialised or preserved.
+ * The call overwrites its outputs (the caller need not zero them).  Integer sums: exact, identical from run to run
+ * (rec_cnt[i] counts list ENTRIES: lists without repeated ids, which is what a ranking is, give users; it stays below 2^32).
+ * Equal ids are combined in LDS bins per workgroup before any global add, the workgroups add into the workspace's copies and
+ * a last launch sums those into the outputs: three launches, no host synchronisation.
+ * Refused before any device work: U < 1, k < 1, k > K, n_items <= 0, a null rankings / gt / count pointer, group_of with
+ * n_groups outside [1, 64], a null or misaligned workspace -> MACR_E_INVALID; then a workspace too small -> MACR_E_WORKSPACE.
+ * -------------------------------------------------------------------------*/
+size_t macr_item_counts_workspace_bytes(int U, int K, int n_items);
+int macr_item_counts(int U, int K, int k, const int32_t *rankings, const int32_t *gt_ptr, const int32_t *gt_idx,
+                     int n_items, const int32_t *group_of, int n_groups, int32_t *rec_cnt, int32_t *hit_cnt,
+                     long long *group_out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Column means of a (rows, cols) matrix in float64 (deterministic tree):
  * the "/ n_test_users" accumulation of macr_mf/train.py:286-290 and the
  * np.mean(all_result, axis=0) of batch_test.py:151.  in_is_f32 selects input

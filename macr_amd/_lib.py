@@ -113,6 +113,8 @@ SIGNATURES = {
     "macr_metrics_mf": (_i, [_i, _i, _p, _p, _p, _p, ctypes.POINTER(ctypes.c_int32), _i, _p, _p]),
     "macr_metrics_mf_mean_workspace_bytes": (_z, [_i, _i]),
     "macr_metrics_mf_mean": (_i, [_i, _i, _p, _p, _p, _p, ctypes.POINTER(ctypes.c_int32), _i, _p, _p, _p, _z, _p]),
+    "macr_item_counts_workspace_bytes": (_z, [_i, _i, _i]),
+    "macr_item_counts": (_i, [_i, _i, _i, _p, _p, _p, _i, _p, _i, _p, _p, _p, _p, _z, _p]),
     "macr_colmean": (_i, [_p, _i, _i, _i, _p, _p]),
 }
 

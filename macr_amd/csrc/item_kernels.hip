@@ -1,0 +1,149 @@
+// Per-item counts of an evaluation's ranking -- the device half of the reference's item_acc_list
+// (macr_mf/train.py:261-277, k = 5; macr_lightgcn/utility/batch_test.py:94-115, k = 20): for every item, how many users
+// have it among their first k ranked ids (rec_cnt) and how many of those hold it in their ground truth (hit_cnt).
+//
+// Form: LDS bins before any global add.  Recommendation lists follow the catalogue's Zipf head -- at
+// 10^7 users x k entries most entries name a few thousand items -- so one global atomic per entry would funnel into a
+// few addresses.  A workgroup keeps an open-addressed table of kItemBins (id -> {rec, hit}) in LDS: an entry claims a
+// slot with one LDS compare-and-swap (or finds its id there) and adds to the slot's 64-bit counter pair with ONE LDS
+// atomic; equal ids of a wave and of the workgroup meet in the slot.  A slot is claimed by the first id that hashes to
+// it, which for a skewed stream is a hot id with overwhelming probability; an entry that finds its kItemProbes slots
+// taken by other ids goes to global memory directly (the cold tail, spread over many addresses).  At the end the
+// workgroup adds each occupied slot to global memory once: a hot item costs one global atomic per workgroup instead of
+// one per entry.  Those adds still meet at the hot items' addresses -- a chain of one add per workgroup, about 0.2 us a
+// link by the first version's time (1 205 workgroups adding straight into the outputs: 252 us at the Gowalla shape) -- so the workgroups add
+// into kItemReplicas copies of a packed {rec, hit} 64-bit counter per item in the workspace (copy = block % kItemReplicas:
+// the chain is an eighth as long, and rec and hit travel in one add), and a last launch sums the copies into the outputs
+// with plain stores and forms the group sums on the way.  Integer adds: the counts are exact and do not depend on the
+// order of arrival.
+#include "common.hpp"
+
+namespace macr {
+
+constexpr int kItemBinBits = 11, kItemBins = 1 << kItemBinBits;   // 2048 slots x (4 + 8) B = 24 KB of LDS
+constexpr int kItemProbes = 4;
+constexpr int kItemThreads = 1024;
+constexpr int kItemMaxBlocks = 1024;      // beyond this a block takes several tiles of 1024 entries: more entries per flush
+constexpr int kItemReplicas = 8;          // copies of the per-item counters the workgroups spread their adds over
+
+__device__ __forceinline__ bool item_in_sorted(const int32_t *a, int n, int32_t x) {
+    int lo = 0, hi = n;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] < x) lo = mid + 1; else hi = mid; }
+    return lo < n && a[lo] == x;
+}
+
+__global__ __launch_bounds__(256) void k_item_zero(unsigned long long *__restrict__ packed, size_t n_words,
+                                                   long long *__restrict__ group_out, int n_group_words) {
+    const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    for (size_t i = t; i < n_words; i += (size_t)gridDim.x * blockDim.x) packed[i] = 0ull;
+    if (group_out && t < (size_t)n_group_words) group_out[t] = 0;
+}
+
+// n_entries = U * k entries (u, p), p < k, entry e = u * k + p, read from rankings[u * K + p]: runs of k consecutive ids.
+// packed: kItemReplicas x n_items counters, low word rec, high word hit (rec <= U < 2^31: no carry into hit)
+__global__ __launch_bounds__(kItemThreads) void k_item_counts(long long n_entries, int K, int k, int n_items,
+                                                              const int32_t *__restrict__ rankings,
+                                                              const int32_t *__restrict__ gt_ptr, const int32_t *__restrict__ gt_idx,
+                                                              unsigned long long *__restrict__ packed) {
+    unsigned long long *mine = packed + (size_t)(blockIdx.x % kItemReplicas) * n_items;
+    __shared__ int32_t keys[kItemBins];
+    __shared__ unsigned long long cnts[kItemBins];       // low word: rec, high word: hit (rec < 2^32 per block: no carry)
+    for (int s = threadIdx.x; s < kItemBins; s += kItemThreads) { keys[s] = -1; cnts[s] = 0ull; }
+    __syncthreads();
+    for (long long e0 = (long long)blockIdx.x * kItemThreads; e0 < n_entries; e0 += (long long)gridDim.x * kItemThreads) {
+        if (e0 + threadIdx.x >= n_entries) continue;
+        // the tile's first user once per wave (uniform 64-bit division), the lane's own by a 32-bit one
+        const long long u0 = n_entries <= 0x7fffffffLL ? (long long)((unsigned)e0 / (unsigned)k) : e0 / k;
+        const unsigned r = (unsigned)(e0 - u0 * k) + threadIdx.x;
+        const long long u = u0 + r / (unsigned)k;
+        const int p = (int)(r % (unsigned)k);
+        const int32_t id = rankings[(size_t)u * K + p];
+        if (id < 0 || id >= n_items) continue;            // -1 = unused slot; an id outside the catalogue is never counted
+        const int a = gt_ptr[u], b = gt_ptr[u + 1];
+        const bool hit = item_in_sorted(gt_idx + a, b - a, id);
+        const unsigned long long inc = hit ? ((1ull << 32) | 1ull) : 1ull;
+        const unsigned h = ((unsigned)id * 2654435761u) >> (32 - kItemBinBits);
+        bool binned = false;
+#pragma unroll
+        for (int probe = 0; probe < kItemProbes && !binned; ++probe) {
+            const int s = (h + probe) & (kItemBins - 1);
+            int32_t owner = keys[s];
+            if (owner == -1) owner = atomicCAS(&keys[s], -1, id);       // -1: this lane claimed the slot
+            if (owner == -1 || owner == id) { atomicAdd(&cnts[s], inc); binned = true; }
+        }
+        if (!binned) atomicAdd(&mine[id], inc);
+    }
+    __syncthreads();
+    for (int s = threadIdx.x; s < kItemBins; s += kItemThreads) {
+        const int32_t id = keys[s];
+        if (id < 0) continue;
+        atomicAdd(&mine[id], cnts[s]);
+    }
+}
+
+// rec_cnt[i], hit_cnt[i] = the sum of item i's copies (plain stores: the outputs need no zero-fill), and with group_of
+// group_out[2 g] += rec, group_out[2 g + 1] += hit over the items of group g (LDS bins, one global add per block and sum)
+__global__ __launch_bounds__(256) void k_item_finish(int n_items, const unsigned long long *__restrict__ packed,
+                                                     const int32_t *__restrict__ group_of, int n_groups,
+                                                     int32_t *__restrict__ rec_cnt, int32_t *__restrict__ hit_cnt,
+                                                     unsigned long long *__restrict__ group_out) {
+    __shared__ unsigned long long sums[128];
+    if (threadIdx.x < 128) sums[threadIdx.x] = 0ull;
+    __syncthreads();
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_items; i += gridDim.x * blockDim.x) {
+        unsigned long long c = 0ull;
+#pragma unroll
+        for (int r = 0; r < kItemReplicas; ++r) c += packed[(size_t)r * n_items + i];
+        const unsigned rec = (unsigned)c, hit = (unsigned)(c >> 32);
+        rec_cnt[i] = (int32_t)rec;
+        hit_cnt[i] = (int32_t)hit;
+        if (!group_out || rec == 0) continue;             // (hit <= rec: nothing to add either)
+        const int g = group_of[i];
+        if (g < 0 || g >= n_groups) continue;             // an item outside every group is in no sum
+        atomicAdd(&sums[2 * g], (unsigned long long)rec);
+        if (hit) atomicAdd(&sums[2 * g + 1], (unsigned long long)hit);
+    }
+    __syncthreads();
+    if (group_out && threadIdx.x < 2 * n_groups && sums[threadIdx.x]) atomicAdd(&group_out[threadIdx.x], sums[threadIdx.x]);
+}
+
+}  // namespace macr
+
+using namespace macr;
+
+extern "C" size_t macr_item_counts_workspace_bytes(int U, int K, int n_items) {
+    if (U <= 0 || K < 1 || n_items <= 0) return 0;
+    return (size_t)kItemReplicas * (size_t)n_items * sizeof(unsigned long long);
+}
+
+extern "C" int macr_item_counts(int U, int K, int k, const int32_t *rankings, const int32_t *gt_ptr, const int32_t *gt_idx,
+                                int n_items, const int32_t *group_of, int n_groups, int32_t *rec_cnt, int32_t *hit_cnt,
+                                long long *group_out, void *workspace, size_t workspace_bytes, void *stream) {
+    hipStream_t st = as_stream(stream);
+    MACR_REQUIRE(U > 0 && K >= 1, MACR_E_INVALID, "item_counts: U=%d K=%d", U, K);
+    MACR_REQUIRE(k >= 1 && k <= K, MACR_E_INVALID, "item_counts: k=%d outside [1, K=%d]", k, K);
+    MACR_REQUIRE(n_items > 0, MACR_E_INVALID, "item_counts: n_items=%d", n_items);
+    MACR_REQUIRE(rankings && gt_ptr && gt_idx && rec_cnt && hit_cnt, MACR_E_INVALID, "item_counts: null pointer");
+    MACR_REQUIRE(!group_of || (n_groups >= 1 && n_groups <= 64), MACR_E_INVALID,
+                 "item_counts: group_of given with n_groups=%d outside [1,64]", n_groups);
+    MACR_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0, MACR_E_INVALID,
+                 "item_counts: workspace is null or not 8-byte aligned (macr_item_counts_workspace_bytes)");
+    MACR_REQUIRE(workspace_bytes >= macr_item_counts_workspace_bytes(U, K, n_items), MACR_E_WORKSPACE,
+                 "item_counts: workspace %zu < %zu bytes", workspace_bytes, macr_item_counts_workspace_bytes(U, K, n_items));
+    const bool groups = group_of && group_out;
+    unsigned long long *packed = static_cast<unsigned long long *>(workspace);
+    const size_t n_words = (size_t)kItemReplicas * n_items;
+    const size_t zb = (n_words + 256 * 8 - 1) / (256 * 8);
+    k_item_zero<<<(unsigned)(zb < 2048 ? zb : 2048), 256, 0, st>>>(packed, n_words, groups ? group_out : nullptr, groups ? 2 * n_groups : 0);
+    MACR_CHECK_LAUNCH("item_zero", st);
+    const long long n_entries = (long long)U * k;
+    const long long tiles = (n_entries + kItemThreads - 1) / kItemThreads;
+    k_item_counts<<<(unsigned)(tiles < kItemMaxBlocks ? tiles : kItemMaxBlocks), kItemThreads, 0, st>>>(
+        n_entries, K, k, n_items, rankings, gt_ptr, gt_idx, packed);
+    MACR_CHECK_LAUNCH("item_counts", st);
+    const int fb = (n_items + 255) / 256 < 1024 ? (n_items + 255) / 256 : 1024;
+    k_item_finish<<<fb, 256, 0, st>>>(n_items, packed, groups ? group_of : nullptr, n_groups, rec_cnt, hit_cnt,
+                                      groups ? reinterpret_cast<unsigned long long *>(group_out) : nullptr);
+    MACR_CHECK_LAUNCH("item_finish", st);
+    return MACR_OK;
+}

@@ -140,6 +140,7 @@ class Evaluator(object):
         seeded: take the thresholds from the seeds, if there are any; mode: None = the complete ranking, "first" / "repair" =
         its two halves (repair_of: the first round's outputs and workspace); filter: None = filter_now."""
         ws = sharding.world()[1]
+        self._last_depth = K
         lo, hi, items_local = self._shard(items_tab)
         branch_local = items_local if branch is None else self._shard(branch)[2]
         filter = filter or self.filter_now
@@ -261,6 +262,25 @@ class Evaluator(object):
         lv, li, _ = ops.topk_merge(vals, idx)                        # merge this shard's splits
         gv, gi = sharding.gather_topk(lv, li)                        # (W,U,K) over RCCL / xGMI
         return ops.topk_merge(gv, gi, fill)
+
+    # ------------------------------------------------------------------ per-item diagnostic (--out 1)
+    def item_accuracy(self, kind, users_tab, user_ids, items_tab, k, w=None, wu=None, c=0.0, branch=None, group_of=None,
+                      n_groups=None):
+        """The counts behind the reference's item_acc_list (macr_mf/train.py:261-277, k = 5; batch_test.py:94-115,
+        k = 20) for the ranking an evaluation with the same arguments scores: (rec_cnt, hit_cnt, group_sums) --
+        int32[n_items] users whose k best non-train items contain the item / those of them whose ground truth holds it,
+        and with group_of (n_items group ids, 0 .. n_groups-1; n_groups None: max + 1) the int64 (n_groups, 2) sums per
+        group, else None.  Ranked by rank() without the -inf fill, at the depth of the evaluator's last ranking when that
+        is deeper than k (one set of seeds serves both); counted on the MERGED ranking, which every rank holds after
+        rank()'s all-gather: correct under item sharding without a collective of its own."""
+        depth = max(int(k), getattr(self, "_last_depth", 0))
+        _, idx, _ = self.rank(kind, users_tab, user_ids, items_tab, depth, w, wu, c, fill_masked=False, branch=branch)
+        if group_of is not None:
+            group_of = torch.as_tensor(np.asarray(group_of.cpu() if torch.is_tensor(group_of) else group_of), dtype=torch.int32)
+            if n_groups is None:
+                n_groups = int(group_of.max()) + 1
+            group_of = group_of.to(self.device).contiguous()
+        return ops.item_counts(idx, self.gt, k, self.n_items, group_of, n_groups or 0)
 
     # ------------------------------------------------------------------ MF flavour
     def test_mf(self, kind, users_tab, user_ids, items_tab, Ks, w=None, wu=None, c=0.0, branch=None):

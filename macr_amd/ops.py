@@ -503,6 +503,25 @@ def metrics_mf_mean(rankings, cnt, gt, Ks, ws, out=None, per_user=False):
     return (m, pu) if per_user else m
 
 
+def item_counts(rankings, gt, k, n_items, group_of=None, n_groups=0):
+    """(U,K) ranked ids (-1 = unused slot) + ground-truth CSR -> (rec_cnt, hit_cnt, group_sums): int32[n_items] users
+    whose first k ids contain the item / those of them whose ground truth holds it (macr_item_counts: the counts behind
+    the reference's item_acc_list, macr_mf/train.py:261-277, batch_test.py:94-115), and with group_of (int32[n_items],
+    values 0 .. n_groups-1) the int64 (n_groups, 2) {rec, hit} sums per group, else None."""
+    U, K = rankings.shape
+    L = _lib.lib()
+    dev = rankings.device
+    rec = torch.empty(n_items, dtype=_i32, device=dev)
+    hit = torch.empty(n_items, dtype=_i32, device=dev)
+    sums = torch.empty((n_groups, 2), dtype=torch.int64, device=dev) if group_of is not None else None
+    need = L.macr_item_counts_workspace_bytes(U, K, n_items)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    check(L.macr_item_counts(U, K, int(k), _ptr(rankings, _i32), _ptr(gt.ptr, _i32), _ptr(gt.idx, _i32), int(n_items),
+                             _ptr(group_of, _i32, True), int(n_groups), _ptr(rec), _ptr(hit), _ptr(sums, None, True),
+                             _ptr(ws, None, True), need, _stream()))
+    return rec, hit, sums
+
+
 def colmean(x, out=None):
     """out: optional float64 device or pinned host tensor of x.shape[1:]"""
     rows = x.shape[0]

@@ -29,7 +29,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from utility.helper import early_stopping, ensureDir          # noqa: E402
 from utility.batch_test import *                              # noqa: E402,F401,F403  (args, data_generator, test ...)
-from utility.branch_ranking import test, test_sweep           # noqa: E402,F811  (+ --test rubi1 / rubi2)
+from utility.branch_ranking import test, test_sweep, item_diagnostic           # noqa: E402,F811  (+ --test rubi1 / rubi2)
 from macr_amd.lightgcn import LightGCN as _LightGCN           # noqa: E402
 from macr_amd.mf import Session                               # noqa: E402
 
@@ -236,19 +236,23 @@ def main(sweep=False):
         elif args.test in ('rubiboth', 'rubi1', 'rubi2'):      # (the same loop over c, LightGCN.py:848-854)
             if main_rank:
                 print('Epoch %d' % epoch)
-            best_hr = 0
+            best_hr, best_c = 0, None
             c_values = np.linspace(args.start, args.end, args.step) if sweep else [args.c]
             rets = test_sweep(sess, model, users_to_test, c_values, method=args.test) if sweep else None
             for k, c in enumerate(c_values):
                 model.update_c(sess, c)
                 ret = rets[k] if sweep else test(sess, model, users_to_test, method=args.test)
                 if ret['hr'][0] > best_hr:
-                    best_hr = ret['hr'][0]
+                    best_hr, best_c = ret['hr'][0], c
                 if args.verbose > 0:
                     perf_str += 'c:%.2f recall=[%.5f, %.5f], hit=[%.5f, %.5f], ndcg=[%.5f, %.5f]\n' % (
                         c, ret['recall'][0], ret['recall'][-1], ret['hr'][0], ret['hr'][-1], ret['ndcg'][0],
                         ret['ndcg'][-1])
             ret['hr'][0] = best_hr
+            if sweep and args.out == 1:                  # the diagnostic of the chosen c only (no hit at any c: the last one)
+                model.update_c(sess, c_values[-1] if best_c is None else best_c)
+                item_diagnostic(sess, model, users_to_test, args.test)
+                model.update_c(sess, c_values[-1])       # (what the loop left, and what a checkpoint records)
             if best_hr > best_c_hr:                      # config['best_c_epoch'] of the reference (:880)
                 best_c_hr, best_c_epoch = best_hr, epoch
             say(perf_str, end='')

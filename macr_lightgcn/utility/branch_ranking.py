@@ -3,19 +3,22 @@ dispatch (batch_test.py:66-84, LightGCN.py:848-854):
     rubi1  rubi_ratings1 (LightGCN.py:442): (y_ui - c) sigmoid(e_i . w), e_i the PROPAGATED item rows
     rubi2  rubi_ratings2 (LightGCN.py:473): the same with the branch factors of the EGO item rows (the scores still read the
            propagated ones)
-Every other method goes to batch_test's own functions unchanged."""
+Every other method goes to batch_test's own functions unchanged.  Under --out 1 every test() is followed by the reference's
+per-item diagnostic of the same ranking (batch_test.py:94-115), item_diagnostic below."""
 import numpy as np
 import torch
 
 from utility import batch_test as _bt
 
-from macr_amd import ops
+from macr_amd import ops, popularity, sharding
 from macr_amd.eval_cache import EvaluatorCache
 from macr_amd.evaluator import Evaluator
 
 # method -> whether the item branch reads the ego rows
 _ITEM_BRANCH = {"rubi1": False, "rubi2": True}
 _evaluators = EvaluatorCache(max_cached=4)
+ITEM_ACC_K, ITEM_ACC_FILE = 20, "Lightgcn_macr.txt"       # heapq.nlargest(20, ...) and the file of batch_test.py:110-115
+_popularity = {}
 
 
 def _evaluator_for(model, users_to_test):
@@ -32,16 +35,45 @@ def _branch(model, method):
 
 
 def test(sess, model, users_to_test, drop_flag=False, train_set_flag=0, method="normal"):
-    """batch_test.test with the methods rubi1 / rubi2 as well"""
+    """batch_test.test with the methods rubi1 / rubi2 as well, and with --out 1 the item diagnostic of the same ranking"""
     if method not in _ITEM_BRANCH:
-        return _bt.test(sess, model, users_to_test, drop_flag, train_set_flag, method)
-    if train_set_flag != 0:
-        raise NotImplementedError("train_set_flag != 0 is unused by the reference CLI")
-    evaluator, uid = _evaluator_for(model, users_to_test)
+        ret = _bt.test(sess, model, users_to_test, drop_flag, train_set_flag, method)
+    else:
+        if train_set_flag != 0:
+            raise NotImplementedError("train_set_flag != 0 is unused by the reference CLI")
+        evaluator, uid = _evaluator_for(model, users_to_test)
+        ua, ia = model.propagated()
+        ret = evaluator.test_lgcn(ops.SCORE_RUBI, ua, uid, ia.contiguous(), model.Ks, model.w, model.w_user, model.rubi_c,
+                                  branch=_branch(model, method))
+        ret = {k: np.asarray(v) for k, v in ret.items()}
+    if _bt.args.out == 1:
+        item_diagnostic(sess, model, users_to_test, method)
+    return ret
+
+
+def item_diagnostic(sess, model, users_to_test, method):
+    """--out 1: the item_acc_list of batch_test.py:94-115 for the ranking test() scores with the same arguments (same score
+    kind, the model's current c -- after a sweep the chosen one), written to Lightgcn_macr.txt as the reference writes it,
+    and one line on the six popularity groups (the cut of macr_mf/load_data.py:424-466 on this loader's train lists).
+    Every rank ranks; the main rank writes and prints."""
+    one_branch = method in _ITEM_BRANCH
+    evaluator, uid = (_evaluator_for if one_branch else _bt._evaluator_for)(model, users_to_test)
+    kind = ops.SCORE_RUBI if one_branch else _bt._METHODS[method]
+    data = _bt.data_generator
+    if not _popularity:
+        counts = np.zeros(_bt.ITEM_NUM, dtype=np.int64)
+        for items in data.train_items.values():
+            np.add.at(counts, np.asarray(items, dtype=np.int64), 1)
+        n_test = np.zeros(_bt.ITEM_NUM, dtype=np.int64)
+        for item, users in data.test_item_set.items():
+            n_test[item] = len(users)
+        _popularity.update(group_of=popularity.item_groups(counts), n_test=n_test)
     ua, ia = model.propagated()
-    ret = evaluator.test_lgcn(ops.SCORE_RUBI, ua, uid, ia.contiguous(), model.Ks, model.w, model.w_user, model.rubi_c,
-                              branch=_branch(model, method))
-    return {k: np.asarray(v) for k, v in ret.items()}
+    rec, hit, sums = evaluator.item_accuracy(kind, ua, uid, ia.contiguous(), ITEM_ACC_K, model.w, model.w_user, model.rubi_c,
+                                             branch=_branch(model, method) if one_branch else None,
+                                             group_of=_popularity["group_of"], n_groups=len(popularity.POINTS) + 1)
+    if sharding.is_main():
+        popularity.emit(rec, hit, sums, _popularity["n_test"], _popularity["group_of"], ITEM_ACC_K, ITEM_ACC_FILE)
 
 
 def test_sweep(sess, model, users_to_test, cs, method="rubiboth"):

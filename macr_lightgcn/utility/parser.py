@@ -44,7 +44,8 @@ _FLAGS = [
     ("start", float, -1., "LightGCN_tune.py: first c of the sweep"),
     ("end", float, 1., "LightGCN_tune.py: last c of the sweep"),
     ("step", int, 20, "LightGCN_tune.py: number of c values"),
-    ("out", int, 0, "(compat)"),
+    ("out", int, 0, "1: every evaluation also computes the per-item accuracy diagnostic of its ranking (Lightgcn_macr.txt, k = 20) and prints "
+                    "the six popularity groups' catalogue share, top-k slot share and recall; 0: off"),
     ("seed", int, 12345, "[new] seed of python/numpy/torch RNGs (the reference hard-codes 12345)"),
     ("resume", int, 0, "[new] 1: load the newest checkpoint of this run's checkpoint directory and continue training"),
     ("sampler", str, "reference", "[new] reference: the reference's random/numpy streams, drawn natively (host); "

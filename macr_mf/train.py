@@ -24,7 +24,7 @@ import torch
 from batch_test import *          # noqa: F401,F403  (args, data, Ks, BATCH_SIZE, ITEM_NUM, USER_NUM)
 from model import BPRMF, Session
 
-from macr_amd import ops
+from macr_amd import ops, popularity
 from macr_amd.evaluator import Evaluator
 from macr_amd.eval_cache import EvaluatorCache
 from macr_amd.metrics_host import (precision_at_k, dcg_at_k, ndcg_at_k, recall_at_k, hit_at_k,   # noqa: F401
@@ -36,6 +36,8 @@ logging.getLogger().setLevel(logging.INFO)
 _MODEL_TYPES = {'o': ops.SCORE_NORMAL, 'rubi_both': ops.SCORE_RUBI_BOTH, 'rubi_c': ops.SCORE_RUBI,
                 'direct_minus_c': ops.SCORE_DIRECT_MINUS}
 _evaluators = EvaluatorCache(max_cached=4)
+ITEM_ACC_K, ITEM_ACC_FILE = 5, "MF_macr.txt"          # heapq.nlargest(5, ...) of train.py:274; the file is this CLI's own
+_n_test = {}
 
 
 def _evaluator_for(model, test_users, valid_set):
@@ -61,10 +63,45 @@ def test(sess, model, test_users, batch_test_flag=False, model_type='o', valid_s
     evaluator, uid = _evaluator_for(model, test_users, valid_set)
     model.sync()
     if getattr(model, "sharded", False):
-        return evaluator.test_mf(_MODEL_TYPES[model_type], model.query_rows(uid), None, model.item_embedding, Ks,
-                                 model.w, model.w_user, model.rubi_c)
-    return evaluator.test_mf(_MODEL_TYPES[model_type], model.user_embedding, uid, model.item_embedding, Ks,
-                             model.w, model.w_user, model.rubi_c)
+        ret = evaluator.test_mf(_MODEL_TYPES[model_type], model.query_rows(uid), None, model.item_embedding, Ks,
+                                model.w, model.w_user, model.rubi_c)
+    else:
+        ret = evaluator.test_mf(_MODEL_TYPES[model_type], model.user_embedding, uid, model.item_embedding, Ks,
+                                model.w, model.w_user, model.rubi_c)
+    if args.out == 1:
+        item_diagnostic(sess, model, test_users, model_type, valid_set)
+    return ret
+
+
+def _item_groups():
+    """group of every item from batch_test's `sorted_id` / `belong` (plot_pics walks train_item_list in insertion order and
+    sorts by count); items without a train interaction: group 0 -- popularity.item_groups of the train counts"""
+    group_of = np.zeros(ITEM_NUM, dtype=np.int32)
+    keys = np.fromiter(data.train_item_list.keys(), dtype=np.int64, count=len(data.train_item_list))
+    group_of[keys[np.asarray(sorted_id, dtype=np.int64)]] = np.asarray(belong, dtype=np.int32)
+    return group_of
+
+
+def item_diagnostic(sess, model, test_users, model_type='o', valid_set="test"):
+    """--out 1: the item_acc_list of train.py:261-277 for the ranking test() scores with the same arguments (same score
+    kind, the model's current c), written to MF_macr.txt, and one line on the six popularity groups of batch_test.py
+    (`belong`; `rate` is the catalogue share of the groups' items that have train interactions).  The denominators count every
+    occurrence of the item in the evaluated file (test_item_list / valid_item_list).  Every rank ranks; the main rank
+    writes and prints."""
+    from macr_amd import sharding
+    evaluator, uid = _evaluator_for(model, test_users, valid_set)
+    model.sync()
+    if valid_set not in _n_test:
+        n_test = np.zeros(ITEM_NUM, dtype=np.int64)
+        for item, users in (data.test_item_list if valid_set == "test" else data.valid_item_list).items():
+            n_test[item] = len(users)
+        _n_test[valid_set] = (n_test, _item_groups())
+    n_test, group_of = _n_test[valid_set]
+    users_tab, ids = (model.query_rows(uid), None) if getattr(model, "sharded", False) else (model.user_embedding, uid)
+    rec, hit, sums = evaluator.item_accuracy(_MODEL_TYPES[model_type], users_tab, ids, model.item_embedding, ITEM_ACC_K,
+                                             model.w, model.w_user, model.rubi_c, group_of=group_of, n_groups=len(rate))
+    if sharding.is_main():
+        popularity.emit(rec, hit, sums, n_test, group_of, ITEM_ACC_K, ITEM_ACC_FILE)
 
 
 def test_sweep(sess, model, test_users, cs, model_type='rubi_both', valid_set="test"):
@@ -272,6 +309,10 @@ def main(sweep=False):
                 if ret['hit_ratio'][0] > best[0]:
                     best = (ret['hit_ratio'][0], ret['recall'][0], ret['precision'][0], ret['ndcg'][0], c)
             ret['hit_ratio'][0], ret['recall'][0], ret['precision'][0], ret['ndcg'][0] = best[:4]
+            if sweep and args.out == 1:              # the diagnostic of the chosen c only (no hit at any c: the last one)
+                model.update_c(sess, best[4] if best[0] > 0 else c_values[-1])
+                item_diagnostic(sess, model, users_to_test, rubi_type, args.valid_set)
+                model.update_c(sess, c_values[-1])   # (what the loop left, and what a checkpoint records)
             if best[0] > config['best_c_hr']:
                 config['best_c_hr'], config['best_c'], config['best_c_epoch'] = best[0], best[4], epoch
         else:
