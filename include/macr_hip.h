@@ -152,8 +152,28 @@ typedef struct macr_hyper {
 #define MACR_STEP_LOSS_ONLY 4    /* macr_lgcn_train_step only: compute the losses, update nothing (see there) */
 #define MACR_STEP_DENSE_LAYERS 8 /* macr_lgcn_train_step only: every propagation layer dense (default: the last forward layer
                                     computes the batch's rows only, the first backward layer gathers from them only) */
+/* MACR_STEP_DETERMINISTIC (additive, abi 16; macr_mf_train_step only): the bit-reproducible step.  CONTRACT: with this flag the
+ * losses, P, Q, w, wu, all Adam slots and adam_pow after the call are a function only of the call's inputs, the library
+ * build and the device model -- never of scheduling: two runs from equal buffers give equal bits.  (The default step sums
+ * gradient rows and branch-vector partial rows with fp32 atomics whose order the hardware picks.)
+ *   - all five MF loss kinds; alone or together with MACR_STEP_DEFER / MACR_STEP_PENDING for the (B,B) kinds (the per-pair
+ *     kinds refuse the deferred bits with MACR_E_INVALID, with or without this flag);
+ *   - every call of a deferred sequence must carry it: the library keeps no state and cannot tell a mixed sequence from a
+ *     uniform one, and a sequence that mixes the two forms is reproducible only up to its last default call.  The two
+ *     forms lay the workspace out differently past its head, so a MACR_STEP_PENDING call must also be of the form of the
+ *     call that deferred.  macr_mf_train_flush takes no flag: the pass it completes is per-row;
+ *   - workspace >= macr_mf_train_workspace_bytes_det(B, d) (>= macr_mf_train_workspace_bytes(B, d); 0 for an unsupported
+ *     d), else MACR_E_WORKSPACE;
+ *   - macr_mf_train_step_lazy refuses it with MACR_E_UNSUPPORTED; the LightGCN steps and every macr_shard_* entry point do
+ *     not know it.
+ * How: every gradient row is staged with plain stores and summed by ONE owner in the order of the (stable) reference sort, at
+ * every B; a row with more references than one chunk is a two-level sum of fixed shape (chunk sums to slots of their own,
+ * then the owner adds the slots in position order); the branch-vector gradient is one partial row per backward block,
+ * folded in block order.  The result differs from the default step's by fp32 rounding only. */
+#define MACR_STEP_DETERMINISTIC 16
 
 size_t macr_mf_train_workspace_bytes(int B, int d);
+size_t macr_mf_train_workspace_bytes_det(int B, int d);
 
 int macr_mf_train_step(int loss_kind, int B, int d, int n_users, int n_items,
                        const int32_t *u, const int32_t *i, const int32_t *j,

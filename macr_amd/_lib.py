@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("MACR_HIP_LIB") or os.path.join(_HERE, "csrc", "libmac
 
 OK, E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_LAUNCH = 0, -1, -2, -3, -4
 LOSS_NORMALBCE, LOSS_RUBIBCEBOTH, LOSS_RUBIBCE, LOSS_BPR, LOSS_BPR_LGCN, LOSS_RUBIBCE_EGO, LOSS_RUBIBPR = 0, 1, 2, 3, 4, 5, 6
-STEP_DEFER, STEP_PENDING, STEP_LOSS_ONLY, STEP_DENSE_LAYERS = 1, 2, 4, 8
+STEP_DEFER, STEP_PENDING, STEP_LOSS_ONLY, STEP_DENSE_LAYERS, STEP_DETERMINISTIC = 1, 2, 4, 8, 16
 SCORE_NORMAL, SCORE_RUBI_BOTH, SCORE_RUBI, SCORE_DIRECT_MINUS, SCORE_DIRECT_MINUS_BOTH = 0, 1, 2, 3, 4
 MAX_TOPK = 128
 MAX_TOPK_FUSED = 32
@@ -56,6 +56,7 @@ SIGNATURES = {
     "macr_timing_begin": (_i, [_p]),
     "macr_timing_end": (_i, [_i, _p, _p]),
     "macr_mf_train_workspace_bytes": (_z, [_i, _i]),
+    "macr_mf_train_workspace_bytes_det": (_z, [_i, _i]),
     "macr_mf_train_step": (_i, [_i] * 5 + [_p] * 3 + [_p] * 12 + [_p] * 4 + [_p, ctypes.POINTER(Hyper), _p, _i, _p, _z, _p]),
     "macr_mf_train_flush": (_i, [_i] * 5 + [_p] * 12 + [_p] * 4 + [ctypes.POINTER(Hyper), _p, _z, _p]),
     "macr_mf_train_step_lazy": (_i, [_i] * 5 + [_p] * 3 + [_p] * 12 + [_p] * 4 + [_p, ctypes.POINTER(Hyper), _p, _i, ctypes.POINTER(LazyAdam), _p, _z, _p]),

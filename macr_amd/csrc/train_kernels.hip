@@ -1484,6 +1484,9 @@ __global__ __launch_bounds__(256) void k_pair_normal(
 // sums its contributions in sorted (= batch) order and stores the row into gP/gQ: the IndexedSlices de-duplication
 // of tf.train.AdamOptimizer (macr_mf/model.py:74), deterministic.  Rows referenced more than kSegChunk times are cut
 // into chunks that add atomically (a handful of atomics for the hottest rows only).
+// MACR_STEP_DETERMINISTIC (include/macr_hip.h) takes this route at EVERY batch size, with those last atomics replaced by an
+// ordered second level (k_seg_reduce<LPR, true> + k_seg_fold) and the branch-vector slots filled by k_branch_fold: the
+// step's results are then a function of its inputs alone.
 // ============================================================================
 constexpr int kSmallBatchMax = 8192;
 
@@ -1549,7 +1552,9 @@ __global__ __launch_bounds__(256) void k_pair_normal_stage(
 // rubibceboth backward; see k_pair_bwd for the arithmetic.  The last block does the step bookkeeping.
 // EGO: see k_pair_bwd<D, true>; the branch scalars dsi, dsj are STAGED like the gradient rows -- sst[o1], sst[o2] -- and
 // summed per row in list order by k_seg_reduce (the determinism of the rows)
-template <int LPR, bool EGO = false, bool RUBIBPR = false>
+// DET (MACR_STEP_DETERMINISTIC): wpart holds one partial row PER BLOCK, [gridDim.x - 1][2][d], stored plainly; k_branch_fold sums
+// them into the kBranchSlots rows the Adam pass reads, in block order
+template <int LPR, bool EGO = false, bool RUBIBPR = false, bool DET = false>
 __global__ __launch_bounds__(256) void k_pair_bwd_stage(
     int B, int Bp, int nrb, int ncb, const int32_t *__restrict__ u, const int32_t *__restrict__ i,
     const int32_t *__restrict__ j, const float *__restrict__ Usrc, const float *__restrict__ Isrc,
@@ -1624,10 +1629,35 @@ __global__ __launch_bounds__(256) void k_pair_bwd_stage(
         const int q = threadIdx.x / LPR, sub = threadIdx.x % LPR;
         float4 acc = make_float4(0, 0, 0, 0);
         for (int k = 0; k < RPB; ++k) acc = add4(acc, s_w[q][k * LPR + sub]);
+        if (DET) {
+            st4(wpart + (size_t)blockIdx.x * 2 * d + (size_t)q * d + 4 * sub, acc);
+            return;
+        }
         float *dst = wpart + (size_t)(blockIdx.x % kBranchSlots) * 2 * d + (size_t)q * d + 4 * sub;
         MACR_ATOMIC_ADD(dst + 0, acc.x); MACR_ATOMIC_ADD(dst + 1, acc.y);
         MACR_ATOMIC_ADD(dst + 2, acc.z); MACR_ATOMIC_ADD(dst + 3, acc.w);
     }
+}
+
+// The branch-vector partial rows of k_pair_bwd_stage<.., DET> (one per block, n2 = 2 d floats each) folded into the
+// kBranchSlots rows of gw: slot s = the rows of blocks s, s + kBranchSlots, ... -- the blocks the default kernel adds into that
+// slot -- summed in block order through four interleaved accumulators: a sum whose shape depends on nblk alone.
+__global__ __launch_bounds__(256) void k_branch_fold(int nblk, int n2, const float *__restrict__ wblk, float *__restrict__ gw) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= kBranchSlots * n2) return;
+    const int s = e / n2, k = e % n2;
+    const float *src = wblk + k;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    int b = s;
+    for (; b + 3 * kBranchSlots < nblk; b += 4 * kBranchSlots) {
+        const float x0 = src[(size_t)b * n2], x1 = src[(size_t)(b + kBranchSlots) * n2];
+        const float x2 = src[(size_t)(b + 2 * kBranchSlots) * n2], x3 = src[(size_t)(b + 3 * kBranchSlots) * n2];
+        a0 += x0; a1 += x1; a2 += x2; a3 += x3;
+    }
+    if (b < nblk) a0 += src[(size_t)b * n2];
+    if (b + kBranchSlots < nblk) a1 += src[(size_t)(b + kBranchSlots) * n2];
+    if (b + 2 * kBranchSlots < nblk) a2 += src[(size_t)(b + 2 * kBranchSlots) * n2];
+    gw[e] = (a0 + a1) + (a2 + a3);
 }
 
 // One LPR-lane group per position p of the sorted reference list.  The group at the head of a chunk -- first
@@ -1636,11 +1666,15 @@ __global__ __launch_bounds__(256) void k_pair_bwd_stage(
 // (runs cut into several chunks).
 // sst / sbr (LightGCN --loss bce2): the item references' staged branch scalars sst[r] are summed per item row the same
 // way, into sbr[row]
-template <int LPR>
+// DET (MACR_STEP_DETERMINISTIC): a chunk of a run cut into several stores its sum to a slot of its own in cpart instead --
+// slot 2 * (p / CH) + (p % CH != 0): at most two such chunks begin in a window of CH positions, the one at its start and the
+// one that reaches its end -- and k_seg_fold gives the row ONE owner that adds the slots in position order.
+template <int LPR, bool DET = false>
 __global__ __launch_bounds__(256) void k_seg_reduce(int n, int n_users, uint32_t key_end, const uint32_t *__restrict__ sk,
                                                     const uint32_t *__restrict__ sv, const float *__restrict__ stage,
                                                     float *gU, float *gI, int32_t *tU, int32_t *tI,
-                                                    const float *__restrict__ sst = nullptr, float *sbr = nullptr) {
+                                                    const float *__restrict__ sst = nullptr, float *sbr = nullptr,
+                                                    float *__restrict__ cpart = nullptr) {
     constexpr int d = 4 * LPR, RPB = RowGroup<LPR>::kRowsPerBlock, CH = LPR < 16 ? LPR : 16;
     RowGroup<LPR> g;
     const long long p = (long long)blockIdx.x * RPB + g.slot;
@@ -1675,13 +1709,15 @@ __global__ __launch_bounds__(256) void k_seg_reduce(int n, int n_users, uint32_t
             acc = add4(acc, ld4(stage + (size_t)r * d + 4 * g.sub));
         }
         float *dst = (is_user ? gU : gI) + row * d + 4 * g.sub;
-        if (multi) {
+        if (DET && multi) {
+            st4(cpart + (size_t)(2 * (p / CH) + ((p % CH) != 0)) * d + 4 * g.sub, acc);
+        } else if (multi) {
             MACR_ATOMIC_ADD(dst + 0, acc.x); MACR_ATOMIC_ADD(dst + 1, acc.y);
             MACR_ATOMIC_ADD(dst + 2, acc.z); MACR_ATOMIC_ADD(dst + 3, acc.w);
         } else {
             st4(dst, acc);
         }
-        if (sst && !is_user) {                     // (wave-uniform pointer) the branch scalars of the run, in list order
+        if (!DET && sst && !is_user) {                     // (wave-uniform pointer) the branch scalars of the run, in list order
             float sb = 0.f;
             for (int k2 = 0; k2 < len; ++k2) sb += sst[__shfl(vs, gbase + k2, kWave)];
             if (g.sub == 0) {
@@ -1692,6 +1728,53 @@ __global__ __launch_bounds__(256) void k_seg_reduce(int n, int n_users, uint32_t
         int32_t *tf = is_user ? tU : tI;           // (a table without flags -- or without rows on this rank -- has none to set)
         if (g.sub == 0 && key0 != prev && tf) tf[row] = 1;
     }
+}
+
+// Second level of k_seg_reduce<LPR, true>: one LPR-lane group per position; the group at the FIRST reference of a row whose run
+// leaves its first chunk owns the row.  Its chunks are the one it begins (slot as above) and one per following window of CH
+// positions that still starts with the row's key (slot 2 * window); the owner adds their sums in position order through four
+// interleaved accumulators, ((a0 + a1) + (a2 + a3)), and stores the row.  The shape of the sum is a function of where the run
+// lies in the sorted list -- of the batch -- and of nothing else; no block waits for another (the launch boundary orders the
+// two levels).  A run of 2048 references is 16-term sums, then 128 terms in four chains of 32.
+template <int LPR>
+__global__ __launch_bounds__(256) void k_seg_fold(int n, int n_users, uint32_t key_end, const uint32_t *__restrict__ sk,
+                                                  const float *__restrict__ cpart, float *gU, float *gI) {
+    constexpr int d = 4 * LPR, RPB = RowGroup<LPR>::kRowsPerBlock, CH = LPR < 16 ? LPR : 16;
+    RowGroup<LPR> g;
+    const long long p = (long long)blockIdx.x * RPB + g.slot;
+    if (p >= n) return;
+    const uint32_t key = sk[p];
+    const uint32_t prev = p > 0 ? sk[p - 1] : 0xffffffffu;
+    if (key >= key_end || key == prev) return;                     // not the first reference of one of this rank's rows
+    const long long w0 = p / CH;
+    // chunk k >= 1 of the run is window w0 + k, if that window starts with the key (sorted: then every window before it does)
+    const long long nwin = ((long long)n + CH - 1) / CH;
+    auto starts = [&](long long w) { return sk[w * CH] == key; };  // w < nwin
+    if (w0 + 1 >= nwin || !starts(w0 + 1)) return;                 // the run ends in its first chunk: k_seg_reduce stored the row
+    // the last such window, by galloping + bisection (the sums below then have a known length and their loads nothing to wait for)
+    long long lo = w0 + 1, step = 1;                               // window lo starts with the key
+    while (lo + step < nwin && starts(lo + step)) { lo += step; step *= 2; }
+    long long hi = lo + step < nwin ? lo + step : nwin;            // window hi does not, or hi == nwin
+    while (lo + 1 < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (starts(mid)) lo = mid; else hi = mid;
+    }
+    const long long nc = lo - w0;                                  // chunks 1 .. nc follow the first
+    const float *src = cpart + 4 * g.sub;
+    auto part = [&](long long k) { return ld4(src + (size_t)(2 * (w0 + k)) * d); };
+    float4 a0 = ld4(src + (size_t)(2 * w0 + ((p % CH) != 0)) * d);
+    float4 a1 = make_float4(0, 0, 0, 0), a2 = a1, a3 = a1;
+    long long k = 1;
+#pragma unroll 2
+    for (; k + 3 <= nc; k += 4) {
+        const float4 x1 = part(k), x2 = part(k + 1), x3 = part(k + 2), x0 = part(k + 3);
+        a1 = add4(a1, x1); a2 = add4(a2, x2); a3 = add4(a3, x3); a0 = add4(a0, x0);
+    }
+    if (k <= nc) a1 = add4(a1, part(k));
+    if (k + 1 <= nc) a2 = add4(a2, part(k + 1));
+    if (k + 2 <= nc) a3 = add4(a3, part(k + 2));
+    const bool is_user = key < (uint32_t)n_users;
+    st4((is_user ? gU : gI) + (size_t)(is_user ? key : key - (uint32_t)n_users) * d + 4 * g.sub, add4(add4(a0, a1), add4(a2, a3)));
 }
 
 // The same de-duplication for a step whose Adam pass follows at once (adam_block INDEXED): nothing is summed for a row
@@ -1939,6 +2022,8 @@ struct PairWs {
     float *colpart;     // [nrb*2*Bp]
     int Bp, nrb, ncb, rows, nblk_pair;
     int nneu, ncbx;     // neutral blocks per row block of the (B,B) launch (0: off); ncbx = ncb + nneu row-sum slabs / loss partials per row block
+    float *cpart;       // deterministic step (carve_pair_ws_det; else NULL): [2 * ceil(3B / CH)][d] chunk sums of k_seg_reduce<LPR, true>
+    float *wblk;        //   and [nblk_bwd][2*d] per-block branch-vector partial rows of k_pair_bwd_stage<.., true>
     size_t bytes;
 };
 
@@ -1975,6 +2060,7 @@ static PairWs carve_pair_ws(void *base, int B, int d, bool force_staged = false,
     const size_t nsort = 3 * (size_t)B;
     w.ska = w.sva = w.skb = w.svb = nullptr;
     w.perm = w.us = w.is = w.js = nullptr; w.ghist = nullptr; w.stage = nullptr; w.n_work = nullptr;
+    w.cpart = w.wblk = nullptr;
     if (w.staged) {
         w.ska = static_cast<uint32_t *>(take(nsort * 4)); w.sva = static_cast<uint32_t *>(take(nsort * 4));
         w.skb = static_cast<uint32_t *>(take(nsort * 4)); w.svb = static_cast<uint32_t *>(take(nsort * 4));
@@ -1986,6 +2072,19 @@ static PairWs carve_pair_ws(void *base, int B, int d, bool force_staged = false,
         w.is = static_cast<int32_t *>(take((size_t)B * 4));   w.js = static_cast<int32_t *>(take((size_t)B * 4));
     }
     w.bytes = off;
+    return w;
+}
+
+// MACR_STEP_DETERMINISTIC: the staged route at every B (whatever MACR_STAGING says), no neutral blocks, and behind it the
+// scratch of the two ordered sums.  scal, gw and fwd lie where carve_pair_ws puts them: macr_mf_train_flush finds them
+// without knowing the mode.
+static PairWs carve_pair_ws_det(void *base, int B, int d) {
+    PairWs w = carve_pair_ws(base, B, d, true, false);
+    const int ch = d / 4 < 16 ? d / 4 : 16;                 // = CH of k_seg_reduce
+    char *p = static_cast<char *>(base);
+    auto take = [&](size_t bytes) { void *r = p ? p + w.bytes : nullptr; w.bytes += align_up(bytes, 256); return r; };
+    w.cpart = static_cast<float *>(take(2 * ((3 * (size_t)B + ch - 1) / ch) * d * 4));
+    w.wblk = static_cast<float *>(take((size_t)w.nblk_bwd * 2 * d * 4));
     return w;
 }
 
@@ -2061,6 +2160,16 @@ static int launch_ref_sort_reduce(int B, int d, int n_urows, int n_irows, const 
     if (sv_sorted) {
         *sv_sorted = r.sv;
         return launch_seg_index(B, d, n_urows, n_irows, r, false, gU, gI, tU, tI, ws, st);
+    }
+    if (ws.cpart) {                       // deterministic step: chunk sums to their own slots, then one owner per row
+        MACR_REQUIRE(!sst, MACR_E_UNSUPPORTED, "pair: the ego branch has no deterministic reduce");
+        MACR_DISPATCH_LPR(d, (k_seg_reduce<LPR, true><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
+                                 n, n_urows, (uint32_t)(n_urows + n_irows), r.sk, r.sv, ws.stage, gU, gI, tU, tI, nullptr, nullptr, ws.cpart)));
+        MACR_CHECK_LAUNCH("seg_reduce", st);
+        MACR_DISPATCH_LPR(d, (k_seg_fold<LPR><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
+                                 n, n_urows, (uint32_t)(n_urows + n_irows), r.sk, ws.cpart, gU, gI)));
+        MACR_CHECK_LAUNCH("seg_fold", st);
+        return MACR_OK;
     }
     MACR_DISPATCH_LPR(d, (k_seg_reduce<LPR><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
                              n, n_urows, (uint32_t)(n_urows + n_irows), r.sk, r.sv, ws.stage, gU, gI, tU, tI, sst, sbr)));
@@ -2165,6 +2274,17 @@ static int launch_pair(int kind, int B, int d, int n_urows, int n_irows, const i
         MACR_CHECK_LAUNCH("pair_bwd", st);
         return launch_ref_sort_reduce(B, d, n_urows, n_irows, u, i, j, gU, gI, tU, tI, ws, st, nullptr, sst, sbr);
     }
+    if (ws.staged && ws.wblk) {           // deterministic step: per-block branch-vector rows, folded in block order
+        MACR_REQUIRE(!listed && !ego, MACR_E_UNSUPPORTED, "pair: the deterministic step is unfused and has no ego branch");
+        MACR_DISPATCH_RUBIBPR(MACR_DISPATCH_LPR(d, (k_pair_bwd_stage<LPR, false, RB, true><<<ws.nblk_bwd + 1, 256, 0, st>>>(
+                                 B, ws.Bp, ws.nrb, ws.ncb, u, i, j, Usrc, Isrc, w, wu, ws.fwd, ws.rowpart, ws.colpart, ws.stage,
+                                 ws.wblk, hp->alpha, hp->beta, coef, adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, L,
+                                 nullptr, 0, tick, ws.nneu))));
+        MACR_CHECK_LAUNCH("pair_bwd", st);
+        k_branch_fold<<<(kBranchSlots * 2 * d + 255) / 256, 256, 0, st>>>(ws.nblk_bwd, 2 * d, ws.wblk, ws.gw);
+        MACR_CHECK_LAUNCH("branch_fold", st);
+        return launch_ref_sort_reduce(B, d, n_urows, n_irows, u, i, j, gU, gI, tU, tI, ws, st, nullptr);
+    }
     if (ws.staged) {
         MACR_DISPATCH_RUBIBPR(MACR_DISPATCH_LPR(d, (k_pair_bwd_stage<LPR, false, RB><<<ws.nblk_bwd + 1, 256, 0, st>>>(
                                  B, ws.Bp, ws.nrb, ws.ncb, u, i, j, Usrc, Isrc, w, wu, ws.fwd, ws.rowpart, ws.colpart, ws.stage,
@@ -2218,6 +2338,12 @@ using namespace macr;
 extern "C" size_t macr_mf_train_workspace_bytes(int B, int d) {
     if (B <= 0 || !dim_supported(d)) return 0;
     return carve_pair_ws(nullptr, B, d).bytes;
+}
+
+extern "C" size_t macr_mf_train_workspace_bytes_det(int B, int d) {
+    if (B <= 0 || !dim_supported(d)) return 0;
+    const size_t det = carve_pair_ws_det(nullptr, B, d).bytes, plain = carve_pair_ws(nullptr, B, d).bytes;
+    return det > plain ? det : plain;         // (macr_mf_train_flush checks the plain size)
 }
 
 namespace macr {
@@ -2284,14 +2410,18 @@ static int mf_train_step(int loss_kind, int B, int d, int n_users, int n_items, 
                      losses && workspace, MACR_E_INVALID, "mf_train_step: null pointer");
     MACR_REQUIRE(is_pair_loss(loss_kind) || (w && wu && mw && vw && mwu && vwu), MACR_E_INVALID,
                  "mf_train_step: rubibceboth needs w, wu and their Adam slots");
-    MACR_REQUIRE((flags & ~(MACR_STEP_DEFER | MACR_STEP_PENDING)) == 0, MACR_E_INVALID, "mf_train_step: flags=%d", flags);
+    MACR_REQUIRE((flags & ~(MACR_STEP_DEFER | MACR_STEP_PENDING | MACR_STEP_DETERMINISTIC)) == 0, MACR_E_INVALID,
+                 "mf_train_step: flags=%d", flags);
+    const bool det = flags & MACR_STEP_DETERMINISTIC;
+    flags &= MACR_STEP_DEFER | MACR_STEP_PENDING;            // from here on: the deferred-mode bits
     MACR_REQUIRE(!flags || !is_pair_loss(loss_kind), MACR_E_INVALID,
                  "mf_train_step: deferred mode exists for the (B,B) losses only (flags=%d)", flags);
+    MACR_REQUIRE(!det || !lz, MACR_E_UNSUPPORTED, "mf_train_step_lazy: the lazy pass has no deterministic mode");
     MACR_REQUIRE(!lz || !is_pair_loss(loss_kind), MACR_E_UNSUPPORTED,
                  "mf_train_step_lazy: the lazy pass rides in the (B,B) launch (rubibceboth, rubibce, rubi)");
     if (int e = validate_hyper(hp, "mf_train_step")) return e;
     if (lz) if (int e = validate_lazy(lz, true, true, "mf_train_step_lazy")) return e;
-    PairWs ws = carve_pair_ws(workspace, B, d, false, loss_kind != MACR_LOSS_RUBIBPR);
+    PairWs ws = det ? carve_pair_ws_det(workspace, B, d) : carve_pair_ws(workspace, B, d, false, loss_kind != MACR_LOSS_RUBIBPR);
     MACR_REQUIRE(workspace_bytes >= ws.bytes, MACR_E_WORKSPACE, "mf_train_step: workspace %zu < %zu bytes",
                  workspace_bytes, ws.bytes);
     MACR_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, MACR_E_INVALID,
@@ -2326,7 +2456,7 @@ static int mf_train_step(int loss_kind, int B, int d, int n_users, int n_items, 
     // a row's staged gradient rows itself instead of reading a row some kernel wrote for it (adam_block INDEXED).
     // (MACR_SEG_UNFUSED=1: the segment reduce writes every row, as in deferred mode -- for A/B measurements and tests.)
     const char *unfused = getenv("MACR_SEG_UNFUSED");
-    const bool indexed = ws.staged && !flags && !lz && (size_t)3 * B <= kRefMaxRefs && !(unfused && unfused[0] == '1');
+    const bool indexed = ws.staged && !det && !flags && !lz && (size_t)3 * B <= kRefMaxRefs && !(unfused && unfused[0] == '1');
     const uint32_t *sv_sorted = nullptr;
     if (int e = launch_pair(loss_kind, B, d, n_users, n_items, u, i, j, P, Q, w, wu, gP, gQ, touchedP, touchedQ, coef, 1,
                             adam_pow, hp, ws, st, pending ? &pa : nullptr, pending ? &a : nullptr, nb, defer ? &L : nullptr,

@@ -20,6 +20,7 @@ Everything else in model.py (userc losses, BIASMF,
 IPS_BPRMF, CausalE) is out of scope and raises NotImplementedError.
 """
 import math
+import os
 
 import numpy as np
 import torch
@@ -36,6 +37,12 @@ class Fetch(object):
 
     def __repr__(self):
         return "<macr fetch %s>" % self.name
+
+
+def deterministic_from_env():
+    """MACR_DETERMINISTIC=1 in the environment: the MF training step runs in its bit-reproducible mode
+    (include/macr_hip.h, MACR_STEP_DETERMINISTIC)"""
+    return os.environ.get("MACR_DETERMINISTIC", "") == "1"
 
 
 def xavier_uniform(shape, generator, device):
@@ -56,7 +63,10 @@ class BPRMF(object):
     # never trains BPR allocates nothing for it)
     _ON_DEMAND = (ops.LOSS_BPR, ops.LOSS_RUBIBPR)
 
-    def __init__(self, args, data_config, device=None, seed=12345, weights=None):
+    def __init__(self, args, data_config, device=None, seed=12345, weights=None, deterministic=None):
+        """deterministic: every training step carries MACR_STEP_DETERMINISTIC -- with the deterministic samplers a seed then pins
+        the run bit for bit.  None: MACR_DETERMINISTIC=1 in the environment decides."""
+        self.deterministic = deterministic_from_env() if deterministic is None else bool(deterministic)
         self.n_users = data_config['n_users']
         self.n_items = data_config['n_items']
         self.decay = args.regs
@@ -83,7 +93,7 @@ class BPRMF(object):
         for train, (suffix, kind) in self._TRAIN.items():
             if kind not in self._ON_DEMAND:
                 self._opt[kind] = ops.MFState(self.weights['user_embedding'], self.weights['item_embedding'],
-                                              self.w, self.w_user, hyper, self.batch_size)
+                                              self.w, self.w_user, hyper, self.batch_size, deterministic=self.deterministic)
             if suffix is None:
                 continue
             for role in ("opt", "loss", "mf_loss", "reg_loss"):        # opt_bce ... ; the BPR graph's plain opt, loss ... (:49-57)
@@ -148,7 +158,8 @@ class BPRMF(object):
         st = self._opt.get(kind)
         if st is None:
             st0 = self._opt[ops.LOSS_NORMALBCE]
-            st = self._opt[kind] = ops.MFState(st0._P, st0._Q, st0.w, st0.wu, st0.hyper, self.batch_size)
+            st = self._opt[kind] = ops.MFState(st0._P, st0._Q, st0.w, st0.wu, st0.hyper, self.batch_size,
+                                               deterministic=self.deterministic)
         return st
 
     def to_device_batch(self, users, pos_items, neg_items):
@@ -233,6 +244,9 @@ class ShardedBPRMF(object):
     _TRAIN = BPRMF._TRAIN
 
     def __init__(self, args, data_config, device=None, seed=12345, layout="interleaved"):
+        if deterministic_from_env():
+            raise NotImplementedError("MACR_DETERMINISTIC=1 has no row-sharded step (--row_shard 1): the macr_shard_* entry points "
+                                      "have no deterministic mode; train unsharded or unset MACR_DETERMINISTIC")
         from . import sharded_train, sharding
         self.n_users, self.n_items = data_config['n_users'], data_config['n_items']
         self.decay, self.emb_dim, self.lr, self.batch_size = args.regs, args.embed_size, args.lr, args.batch_size

@@ -12,7 +12,7 @@ import torch
 from . import _lib
 from ._lib import (LOSS_NORMALBCE, LOSS_RUBIBCEBOTH, LOSS_RUBIBCE, LOSS_BPR, LOSS_BPR_LGCN, LOSS_RUBIBCE_EGO, LOSS_RUBIBPR, SCORE_NORMAL, SCORE_RUBI_BOTH, SCORE_RUBI,  # noqa: F401
                    SCORE_DIRECT_MINUS, SCORE_DIRECT_MINUS_BOTH, MAX_TOPK,
-                   Hyper, MacrError, check, is_pair_loss)
+                   STEP_DETERMINISTIC, Hyper, MacrError, check, is_pair_loss)
 
 
 def _stream(device_index=None):
@@ -601,12 +601,18 @@ class MFState(object):
     P,Q,w,wu mirror weights['user_embedding'], ['item_embedding'], self.w, self.w_user of
     macr_mf/model.py:107-122,:59-60.  Adam slots start at zero, beta powers at (beta1,beta2)."""
 
-    def __init__(self, P, Q, w, wu, hyper, batch_cap, lazy_period=None):
+    def __init__(self, P, Q, w, wu, hyper, batch_cap, lazy_period=None, deterministic=False):
         """lazy_period: K of the lazy dense Adam pass in deferred mode (include/macr_hip.h: macr_lazy_adam; 1 = the dense pass
-        every step); None: the environment's MACR_LAZY_ADAM_MF, else by table and batch size (mf_lazy_period_for)"""
+        every step); None: the environment's MACR_LAZY_ADAM_MF, else by table and batch size (mf_lazy_period_for)
+        deterministic: every step carries MACR_STEP_DETERMINISTIC (include/macr_hip.h): losses, tables, slots and beta powers
+        are a function of the inputs alone, bit for bit.  The Adam pass is then the dense one (lazy_period 1), whatever the
+        table size or MACR_LAZY_ADAM_MF says: the lazy pass has no deterministic form."""
         _require_f32(P=P, Q=Q, w=w, wu=wu)
         dev = P.device
-        if lazy_period is None and os.environ.get("MACR_LAZY_ADAM_MF", ""):
+        self.deterministic = bool(deterministic)
+        if self.deterministic:
+            lazy_period = 1
+        elif lazy_period is None and os.environ.get("MACR_LAZY_ADAM_MF", ""):
             lazy_period = int(os.environ["MACR_LAZY_ADAM_MF"])
         self.lazy_period = lazy_period        # None: decided per deferred sequence from its batch size
         self._seq_lazy = None                 # struct macr_lazy_adam of the running deferred sequence (None: the dense form)
@@ -632,7 +638,8 @@ class MFState(object):
     def reserve(self, B):
         if B > self.batch_cap:
             self.flush()                 # a pending pass keeps lr_t and partial rows in the old workspace
-            nbytes = _lib.lib().macr_mf_train_workspace_bytes(B, self.d)
+            size_of = _lib.lib().macr_mf_train_workspace_bytes_det if self.deterministic else _lib.lib().macr_mf_train_workspace_bytes
+            nbytes = size_of(B, self.d)
             if nbytes == 0:
                 raise MacrError(_lib.E_UNSUPPORTED, "embed_size %d not in {32,64,128,256}" % self.d)
             self.ws = torch.empty(nbytes, dtype=torch.uint8, device=self._P.device)
@@ -697,6 +704,8 @@ class MFState(object):
         if self.pending_B and kind != self.pending_kind:
             self.flush()
         flags = (_lib.STEP_DEFER if defer else 0) | (_lib.STEP_PENDING if self.pending_B else 0)
+        if self.deterministic:                  # on every call of a sequence
+            flags |= _lib.STEP_DETERMINISTIC
         tabs = self._tables()
         if not self.pending_B:                  # a deferred sequence starts (or a single complete step): its form
             self._seq_lazy = self._lazy_struct(B) if defer else None
