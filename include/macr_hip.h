@@ -152,7 +152,7 @@ typedef struct macr_hyper {
 #define MACR_STEP_LOSS_ONLY 4    /* macr_lgcn_train_step only: compute the losses, update nothing (see there) */
 #define MACR_STEP_DENSE_LAYERS 8 /* macr_lgcn_train_step only: every propagation layer dense (default: the last forward layer
                                     computes the batch's rows only, the first backward layer gathers from them only) */
-/* MACR_STEP_DETERMINISTIC (additive, abi 16; macr_mf_train_step only): the bit-reproducible step.  CONTRACT: with this flag the
+/* MACR_STEP_DETERMINISTIC (additive, abi 16; macr_mf_train_step, macr_lgcn_train_step, macr_lgcn_train_step_t): the bit-reproducible step.  CONTRACT: with this flag the
  * losses, P, Q, w, wu, all Adam slots and adam_pow after the call are a function only of the call's inputs, the library
  * build and the device model -- never of scheduling: two runs from equal buffers give equal bits.  (The default step sums
  * gradient rows and branch-vector partial rows with fp32 atomics whose order the hardware picks.)
@@ -164,12 +164,27 @@ typedef struct macr_hyper {
  *     call that deferred.  macr_mf_train_flush takes no flag: the pass it completes is per-row;
  *   - workspace >= macr_mf_train_workspace_bytes_det(B, d) (>= macr_mf_train_workspace_bytes(B, d); 0 for an unsupported
  *     d), else MACR_E_WORKSPACE;
- *   - macr_mf_train_step_lazy refuses it with MACR_E_UNSUPPORTED; the LightGCN steps and every macr_shard_* entry point do
- *     not know it.
+ *   - macr_mf_train_step_lazy refuses it with MACR_E_UNSUPPORTED; the macr_shard_* entry points do not know it.
  * How: every gradient row is staged with plain stores and summed by ONE owner in the order of the (stable) reference sort, at
  * every B; a row with more references than one chunk is a two-level sum of fixed shape (chunk sums to slots of their own,
  * then the owner adds the slots in position order); the branch-vector gradient is one partial row per backward block,
- * folded in block order.  The result differs from the default step's by fp32 rounding only. */
+ * folded in block order.  The result differs from the default step's by fp32 rounding only.
+ *
+ * macr_lgcn_train_step / macr_lgcn_train_step_t: the same CONTRACT for losses[3], T, w, wu, mT, vT, mw, vw, mwu, vwu and adam_pow
+ * after the call and for the regions of the workspace that are zero between steps.
+ *   - all five LightGCN loss kinds; alone or together with MACR_STEP_LOSS_ONLY and / or MACR_STEP_DENSE_LAYERS (a loss-only
+ *     call gives its three losses the same guarantee and writes nothing else); every n_layers, symmetric and transposed
+ *     adjacency, with or without a plan, any plan (row plan, octants on or off, entry stream);
+ *   - workspace >= macr_lgcn_train_workspace_bytes_det(B, N, d, plan_host) / _det_t(.., plan_t_host) (>= the plain sizes; 0
+ *     where those are 0), else MACR_E_WORKSPACE.  Its layout is the plain one (zero it once, as the plain one) with the pair
+ *     stage staged at every B and scratch behind it that every step rewrites before it reads it.
+ * How: the pair stage as above (the gradient rows into dE; --loss bce2: the staged branch scalars of the ego item rows in the
+ * same two levels, chunk sums beside the chunk rows' slots).  The ego-row regulariser and emb_loss have one owner per
+ * distinct row of the batch -- the first position of its run in the sorted reference list, which knows the run's length c:
+ * G[row] += coef c T[row] with plain stores where the layers are dense, (double) c |T[row]|^2 summed per block and folded
+ * in block order; the fused epilogues of the last backward layer run in instantiations that do not add into the emb_loss
+ * slots.  The propagation itself is order-fixed in both modes: one wave owns a row, and a hub row's pieces are published
+ * to the slab and summed by the last arriver in slot order, whichever wave that is. */
 #define MACR_STEP_DETERMINISTIC 16
 
 size_t macr_mf_train_workspace_bytes(int B, int d);
@@ -452,11 +467,12 @@ int macr_lgcn_propagate(int N, int d, int n_layers, const int32_t *rowptr, const
  *          before its first use (the batch-row flags and the hub rows' arrival counters are zero
  *          between steps: every step leaves them that way)
  *   losses (dev) fp32[3] = {loss, mf_loss, emb_loss}
- *   flags  0, or MACR_STEP_LOSS_ONLY: sess.run([loss_X, mf_loss_X, emb_loss_X]) without opt_X -- the
+ *   flags  0, or MACR_STEP_DENSE_LAYERS, MACR_STEP_DETERMINISTIC (see their definitions), or MACR_STEP_LOSS_ONLY: sess.run([loss_X, mf_loss_X, emb_loss_X]) without opt_X -- the
  *          reference's per-log-interval "test loss" pass (LightGCN.py:799-819, train_thread_test :620-647):
  *          propagation + forward of the loss; T, w, wu, the slots and adam_pow are left untouched.
  * -------------------------------------------------------------------------*/
 size_t macr_lgcn_train_workspace_bytes(int B, int N, int d, const void *plan_host);
+size_t macr_lgcn_train_workspace_bytes_det(int B, int N, int d, const void *plan_host);      /* MACR_STEP_DETERMINISTIC (see there) */
 
 int macr_lgcn_train_step(int loss_kind, int B, int d, int n_users, int n_items, int n_layers,
                          const int32_t *rowptr, const int32_t *col, const float *val,
@@ -473,6 +489,7 @@ int macr_lgcn_train_step(int loss_kind, int B, int d, int n_users, int n_items, 
  * plan of its own (both plans or neither); the forward propagation uses A, the backward propagation A^T.  macr_lgcn_train_step is
  * this call with A in both places.  workspace >= macr_lgcn_train_workspace_bytes_t(B, N, d, plan_host, plan_t_host). */
 size_t macr_lgcn_train_workspace_bytes_t(int B, int N, int d, const void *plan_host, const void *plan_t_host);
+size_t macr_lgcn_train_workspace_bytes_det_t(int B, int N, int d, const void *plan_host, const void *plan_t_host);
 int macr_lgcn_train_step_t(int loss_kind, int B, int d, int n_users, int n_items, int n_layers,
                            const int32_t *rowptr, const int32_t *col, const float *val,
                            const void *plan_dev, const void *plan_host,

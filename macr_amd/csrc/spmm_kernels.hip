@@ -110,7 +110,8 @@ struct AdamFuse {
     const StepScalars *scal;      // lr_t of this step (written by pair_bwd)
     float b1, b2, eps, coef;      // coef = decay / batch_size
     float *dE;                    // gradient buffer of the pair kernels (rows of the batch are zeroed)
-    double *emb_acc;              // [2048] partial sums of cnt * |T row|^2 (emb_loss), slot = row % 2048
+    double *emb_acc;              // [2048] partial sums of cnt * |T row|^2 (emb_loss), slot = row % 2048 (fp64 atomics: the order
+                                  // of arrival shows in the last bits).  NULL: the epilogues leave it alone (the deterministic step)
     float *sb;                    // NULL, or (LightGCN --loss bce2) a scalar per row: the row's gradient also gets sb[r] * bw, and
     const float *bw;              // sb[r] is zeroed -- the item branch on the EGO rows, which does not pass through the propagation
 };
@@ -288,7 +289,8 @@ __device__ __forceinline__ void gather_batches_masked(int cv, float av, uint64_t
 // (broadcast ds_read_b64), the 32 gathers and the rows' S_in / optimizer operands fly together, R epilogues follow.  Two
 // dependent trips for up to eight rows instead of three per row; 20 k waves instead of 51 k.  Same arithmetic per row (CSR
 // order, one fma chain).  6.6 MB of plan for the Yelp2018-shape graph.
-template <int D, int R, bool FUSE>
+// EMB = false (MACR_STEP_DETERMINISTIC): a FUSE epilogue that leaves emb_acc alone -- emb_loss then comes from k_reg_rows / k_emb_fold
+template <int D, int R, bool FUSE, bool EMB = true>
 __device__ __forceinline__ void spmm_records(const int32_t *__restrict__ rec, const float *__restrict__ X, float *Y, const float *S_in,
                                              float *S_out, float scale, int32_t *sp_rows, float *fT, float *fm, float *fv,
                                              const StepScalars *__restrict__ fscal, float *fdE, double *femb, float b1, float b2,
@@ -354,7 +356,8 @@ __device__ __forceinline__ void spmm_records(const int32_t *__restrict__ rec, co
             if (cr) {
                 sq = wave_sum(sq);
                 if (lane == 0) {
-                    atomicAdd(femb + (row[q] & 2047), (double)cr * (double)sq); sp_rows[row[q]] = 0;
+                    if (EMB) atomicAdd(femb + (row[q] & 2047), (double)cr * (double)sq);
+                    sp_rows[row[q]] = 0;
                     if (fsb) fsb[row[q]] = 0.f;
                 }
             }
@@ -382,7 +385,7 @@ struct SpmmScalars {
     int n_single, n_rec8, n_rec4, n_rec2, n_rec1;   // RECORDS (dense layers at d = 64; n_single = 0: off): waves [0, n_single) take one
                                   // item each, the waves behind them one record each, class by class
 };
-template <int D, int SPARSE, bool FUSE>
+template <int D, int SPARSE, bool FUSE, bool EMB = true>
 __global__ __launch_bounds__(256) void k_spmm_row(const SpmmScalars P, const int32_t *__restrict__ rowptr,
                                                   const int32_t *__restrict__ col, const float *__restrict__ val,
                                                   const int4 *__restrict__ items, const int32_t *__restrict__ slot_group,
@@ -447,10 +450,10 @@ __global__ __launch_bounds__(256) void k_spmm_row(const SpmmScalars P, const int
             const int k = w - P.n_single;
             const int32_t *rec = records + (size_t)k * kRecInts;
 #define MACR_REC_ARGS rec, X, Y, S_in, S_out, P.scale, sp_cnt, fT, fm, fv, fscal, fdE, femb, P.b1, P.b2, P.eps, P.coef, w, fsb, fbw
-            if (k < P.n_rec8) spmm_records<D, 8, FUSE>(MACR_REC_ARGS);
-            else if (k < P.n_rec8 + P.n_rec4) spmm_records<D, 4, FUSE>(MACR_REC_ARGS);
-            else if (k < P.n_rec8 + P.n_rec4 + P.n_rec2) spmm_records<D, 2, FUSE>(MACR_REC_ARGS);
-            else if (k < P.n_rec8 + P.n_rec4 + P.n_rec2 + P.n_rec1) spmm_records<D, 1, FUSE>(MACR_REC_ARGS);
+            if (k < P.n_rec8) spmm_records<D, 8, FUSE, EMB>(MACR_REC_ARGS);
+            else if (k < P.n_rec8 + P.n_rec4) spmm_records<D, 4, FUSE, EMB>(MACR_REC_ARGS);
+            else if (k < P.n_rec8 + P.n_rec4 + P.n_rec2) spmm_records<D, 2, FUSE, EMB>(MACR_REC_ARGS);
+            else if (k < P.n_rec8 + P.n_rec4 + P.n_rec2 + P.n_rec1) spmm_records<D, 1, FUSE, EMB>(MACR_REC_ARGS);
 #undef MACR_REC_ARGS
             return;
         }
@@ -643,7 +646,7 @@ __global__ __launch_bounds__(256) void k_spmm_row(const SpmmScalars P, const int
         if (c) {                                                 // wave-uniform
             sq = wave_sum(sq);
             if (lane == 0) {
-                atomicAdd(femb + (r & 2047), (double)c * (double)sq);
+                if (EMB) atomicAdd(femb + (r & 2047), (double)c * (double)sq);
                 A.sp.rows[r] = 0;
                 if (fsb) fsb[r] = 0.f;
             }
@@ -739,7 +742,7 @@ struct StreamArgs {
 };
 
 // One row's result: Y = A X, S_out = (S_in + A X) * scale -- or, FUSE, the optimizer on T[r] (see AdamFuse).
-template <int D, bool FUSE>
+template <int D, bool FUSE, bool EMB = true>
 __device__ __forceinline__ void stream_row_out(int r, const float (&acc)[RowGeom<D>::NV], const float (&s)[RowGeom<D>::NV],
                                                int lane, float scale) {
     constexpr int NV = RowGeom<D>::NV;
@@ -768,7 +771,7 @@ __device__ __forceinline__ void stream_row_out(int r, const float (&acc)[RowGeom
         if (c) {                                                 // wave-uniform
             sq = wave_sum(sq);
             if (lane == 0) {
-                atomicAdd(ka->fz.emb + (r & 2047), (double)c * (double)sq);
+                if (EMB) atomicAdd(ka->fz.emb + (r & 2047), (double)c * (double)sq);
                 cnt[r] = 0;
             }
         }
@@ -783,7 +786,7 @@ __device__ __forceinline__ void stream_row_out(int r, const float (&acc)[RowGeom
     }
 }
 
-template <int D, bool FUSE>
+template <int D, bool FUSE, bool EMB = true>
 __global__ __launch_bounds__(256) void k_spmm_stream(const StreamArgs A) {
     const int4 *__restrict__ chunk_desc = A.chunk_desc;
     const int32_t *__restrict__ empties = A.empties;
@@ -825,7 +828,7 @@ __global__ __launch_bounds__(256) void k_spmm_stream(const StreamArgs A) {
         float s[NV];
 #pragma unroll
         for (int v = 0; v < NV; ++v) s[v] = S_in[(size_t)r * D + lane + 64 * v];
-        stream_row_out<D, FUSE>(r, zero, s, lane, P.scale);
+        stream_row_out<D, FUSE, EMB>(r, zero, s, lane, P.scale);
     }
     float acc[NV];
 #pragma unroll
@@ -868,7 +871,7 @@ __global__ __launch_bounds__(256) void k_spmm_stream(const StreamArgs A) {
 #pragma unroll
                 for (int v = 0; v < NV; ++v) acc[v] = fmaf(wgt[8 * g + 7], x[8 * g + 7][v], acc[v]);
             } else if (__builtin_amdgcn_readfirstlane(__float_as_int(wgt[8 * g + 7])) == 0) {   // the row's end marker: x = S_in of the row
-                stream_row_out<D, FUSE>(c7 & 0x7fffffff, acc, x[8 * g + 7], lane, P.scale);
+                stream_row_out<D, FUSE, EMB>(c7 & 0x7fffffff, acc, x[8 * g + 7], lane, P.scale);
 #pragma unroll
                 for (int v = 0; v < NV; ++v) acc[v] = 0.f;
             }                                                    // (weight bits 1: the end of a piece, always its chunk's last entry)
@@ -945,7 +948,7 @@ __global__ __launch_bounds__(256) void k_spmm_stream(const StreamArgs A) {
     float s[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) s[v] = S_in[(size_t)r * D + lane + 64 * v];
-    stream_row_out<D, FUSE>(r, acc, s, lane, P.scale);
+    stream_row_out<D, FUSE, EMB>(r, acc, s, lane, P.scale);
 }
 
 // out = in * scale   (n_layers == 0 degenerate case) -- float4 per lane
@@ -1049,7 +1052,8 @@ int launch_propagate(int N, int d, int n_layers, const int32_t *rowptr, const in
 #define MACR_STREAM_ARGS sa
 #define MACR_STREAM_ROW(D_)                                                                       \
     do {                                                                                          \
-        if (fused) k_spmm_stream<D_, true><<<sgrid, 256, 0, st>>>(MACR_STREAM_ARGS);              \
+        if (fused && !af.emb_acc) k_spmm_stream<D_, true, false><<<sgrid, 256, 0, st>>>(MACR_STREAM_ARGS); \
+        else if (fused) k_spmm_stream<D_, true><<<sgrid, 256, 0, st>>>(MACR_STREAM_ARGS);         \
         else k_spmm_stream<D_, false><<<sgrid, 256, 0, st>>>(MACR_STREAM_ARGS);                   \
     } while (0)
             switch (d) {
@@ -1079,6 +1083,7 @@ int launch_propagate(int N, int d, int n_layers, const int32_t *rowptr, const in
     do {                                                                                                          \
         if (mode == kSparseOut) k_spmm_row<D_, kSparseOut, false><<<grid, 256, 0, st>>>(MACR_SPMM_ARGS);          \
         else if (mode == kSparseIn) k_spmm_row<D_, kSparseIn, false><<<grid, 256, 0, st>>>(MACR_SPMM_ARGS);       \
+        else if (fused && !af.emb_acc) k_spmm_row<D_, kDense, true, false><<<rgrid, 256, 0, st>>>(MACR_SPMM_ARGS); \
         else if (fused) k_spmm_row<D_, kDense, true><<<rgrid, 256, 0, st>>>(MACR_SPMM_ARGS);                       \
         else k_spmm_row<D_, kDense, false><<<rgrid, 256, 0, st>>>(MACR_SPMM_ARGS);                                 \
     } while (0)

@@ -1665,7 +1665,7 @@ __global__ __launch_bounds__(256) void k_branch_fold(int nblk, int n2, const flo
 // stores the row (whole run in one chunk: plain store; gP/gQ rows are zero between steps) or adds it atomically
 // (runs cut into several chunks).
 // sst / sbr (LightGCN --loss bce2): the item references' staged branch scalars sst[r] are summed per item row the same
-// way, into sbr[row]
+// way, into sbr[row] (DET: the chunk sums of a cut run to spart, one float per cpart slot)
 // DET (MACR_STEP_DETERMINISTIC): a chunk of a run cut into several stores its sum to a slot of its own in cpart instead --
 // slot 2 * (p / CH) + (p % CH != 0): at most two such chunks begin in a window of CH positions, the one at its start and the
 // one that reaches its end -- and k_seg_fold gives the row ONE owner that adds the slots in position order.
@@ -1674,7 +1674,7 @@ __global__ __launch_bounds__(256) void k_seg_reduce(int n, int n_users, uint32_t
                                                     const uint32_t *__restrict__ sv, const float *__restrict__ stage,
                                                     float *gU, float *gI, int32_t *tU, int32_t *tI,
                                                     const float *__restrict__ sst = nullptr, float *sbr = nullptr,
-                                                    float *__restrict__ cpart = nullptr) {
+                                                    float *__restrict__ cpart = nullptr, float *__restrict__ spart = nullptr) {
     constexpr int d = 4 * LPR, RPB = RowGroup<LPR>::kRowsPerBlock, CH = LPR < 16 ? LPR : 16;
     RowGroup<LPR> g;
     const long long p = (long long)blockIdx.x * RPB + g.slot;
@@ -1717,11 +1717,12 @@ __global__ __launch_bounds__(256) void k_seg_reduce(int n, int n_users, uint32_t
         } else {
             st4(dst, acc);
         }
-        if (!DET && sst && !is_user) {                     // (wave-uniform pointer) the branch scalars of the run, in list order
+        if (sst && !is_user) {                             // (wave-uniform pointer) the branch scalars of the run, in list order
             float sb = 0.f;
             for (int k2 = 0; k2 < len; ++k2) sb += sst[__shfl(vs, gbase + k2, kWave)];
             if (g.sub == 0) {
-                if (multi) MACR_ATOMIC_ADD(sbr + row, sb);
+                if (DET && multi) spart[2 * (p / CH) + ((p % CH) != 0)] = sb;       // (the slot beside the chunk's cpart slot)
+                else if (multi) MACR_ATOMIC_ADD(sbr + row, sb);
                 else sbr[row] = sb;
             }
         }
@@ -1738,7 +1739,8 @@ __global__ __launch_bounds__(256) void k_seg_reduce(int n, int n_users, uint32_t
 // two levels).  A run of 2048 references is 16-term sums, then 128 terms in four chains of 32.
 template <int LPR>
 __global__ __launch_bounds__(256) void k_seg_fold(int n, int n_users, uint32_t key_end, const uint32_t *__restrict__ sk,
-                                                  const float *__restrict__ cpart, float *gU, float *gI) {
+                                                  const float *__restrict__ cpart, float *gU, float *gI,
+                                                  const float *__restrict__ spart = nullptr, float *sbr = nullptr) {
     constexpr int d = 4 * LPR, RPB = RowGroup<LPR>::kRowsPerBlock, CH = LPR < 16 ? LPR : 16;
     RowGroup<LPR> g;
     const long long p = (long long)blockIdx.x * RPB + g.slot;
@@ -1775,6 +1777,19 @@ __global__ __launch_bounds__(256) void k_seg_fold(int n, int n_users, uint32_t k
     if (k + 2 <= nc) a3 = add4(a3, part(k + 2));
     const bool is_user = key < (uint32_t)n_users;
     st4((is_user ? gU : gI) + (size_t)(is_user ? key : key - (uint32_t)n_users) * d + 4 * g.sub, add4(add4(a0, a1), add4(a2, a3)));
+    if (spart && !is_user && g.sub == 0) {                         // (LightGCN --loss bce2) the row's branch scalar: the same slots, the same shape
+        auto sp = [&](long long k) { return spart[2 * (w0 + k)]; };
+        float b0 = spart[2 * w0 + ((p % CH) != 0)], b1 = 0.f, b2 = 0.f, b3 = 0.f;
+        long long k = 1;
+        for (; k + 3 <= nc; k += 4) {
+            const float x1 = sp(k), x2 = sp(k + 1), x3 = sp(k + 2), x0 = sp(k + 3);
+            b1 += x1; b2 += x2; b3 += x3; b0 += x0;
+        }
+        if (k <= nc) b1 += sp(k);
+        if (k + 1 <= nc) b2 += sp(k + 1);
+        if (k + 2 <= nc) b3 += sp(k + 2);
+        sbr[key - (uint32_t)n_users] = (b0 + b1) + (b2 + b3);
+    }
 }
 
 // The same de-duplication for a step whose Adam pass follows at once (adam_block INDEXED): nothing is summed for a row
@@ -1961,6 +1976,69 @@ __global__ __launch_bounds__(256) void k_ego_branch_rows(int n, const float *__r
     if (g.sub == 0) sbr[r] = 0.f;
 }
 
+// MACR_STEP_DETERMINISTIC: the ego-row regulariser and emb_loss with ONE owner per distinct row of the batch, behind the
+// reference sort (sk: the 3B sorted keys = rows of T).  One LPR-lane group per position; the group at the first position of a
+// run owns the row and learns its multiplicity c -- the run's length, by galloping + bisection over the sorted keys.
+//   G != NULL (dense layers, after the backward propagation wrote G): G[row] += (coef c) T[row], plain loads and stores --
+//   what k_reg_scatter adds with c atomics per element;
+//   the row's share (double) c |T[row]|^2 of emb_loss: summed per block in slot order, one double per block to epart.
+// T is read before any Adam update of the step.  Every slot of epart is rewritten by every step.
+template <int LPR>
+__global__ __launch_bounds__(256) void k_reg_rows(int n, const uint32_t *__restrict__ sk, const float *__restrict__ T, float *G,
+                                                  float coef, double *__restrict__ epart) {
+    constexpr int d = 4 * LPR, RPB = RowGroup<LPR>::kRowsPerBlock;
+    __shared__ double s_e[RPB];
+    RowGroup<LPR> g;
+    const long long p = (long long)blockIdx.x * RPB + g.slot;
+    uint32_t key = 0;
+    long long c = 0;                                               // 0: not the first reference of a row
+    if (p < n) {
+        key = sk[p];
+        if (p == 0 || sk[p - 1] != key) {
+            long long lo = p, step = 1;                            // position lo holds the key
+            while (lo + step < n && sk[lo + step] == key) { lo += step; step *= 2; }
+            long long hi = lo + step < n ? lo + step : n;          // position hi does not, or hi == n
+            while (lo + 1 < hi) {
+                const long long mid = (lo + hi) >> 1;
+                if (sk[mid] == key) lo = mid; else hi = mid;
+            }
+            c = lo - p + 1;
+        }
+    }
+    float4 x = make_float4(0, 0, 0, 0);
+    if (c) x = ld4(T + (size_t)key * d + 4 * g.sub);
+    const float sq = group_sum<LPR>(dot4(x, x));                   // (every lane of the wave takes part; the groups of non-owners sum zeros)
+    if (c && G) {
+        float *row = G + (size_t)key * d + 4 * g.sub;
+        st4(row, fma4(coef * (float)c, x, ld4(row)));
+    }
+    if (g.sub == 0) s_e[g.slot] = (double)c * (double)sq;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double e = 0.0;
+#pragma unroll
+        for (int k = 0; k < RPB; ++k) e += s_e[k];
+        epart[blockIdx.x] = e;
+    }
+}
+
+// emb_loss of the deterministic step: the n block sums of k_reg_rows in a sum of fixed shape (thread t: slots t, t + 256, ...
+// in order; then the threads' sums by the shuffle tree of each wave, the four waves in order).  out_d: a double (slot 0 of
+// emb_acc, whose other slots are zero: k_lgcn_finalize reads and clears it); out_f: a float partial for finalize_losses.
+__global__ __launch_bounds__(256) void k_emb_fold(int n, const double *__restrict__ epart, double *out_d, float *out_f) {
+    __shared__ double s_sq[4];
+    double e = 0.0;
+    for (int k = threadIdx.x; k < n; k += 256) e += epart[k];
+    e = wave_sum_d(e);
+    if ((threadIdx.x & 63) == 0) s_sq[threadIdx.x >> 6] = e;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double s = ((s_sq[0] + s_sq[1]) + s_sq[2]) + s_sq[3];
+        if (out_d) out_d[0] = s;
+        if (out_f) out_f[0] = (float)s;
+    }
+}
+
 __global__ __launch_bounds__(256) void k_lgcn_finalize(AdamArgs a, const StepScalars *scal, LossArgs L, double *emb_acc) {
     __shared__ float4 s_red[256];
     if (blockIdx.x < a.n_seg) { adam_block<true>(a, a.seg[blockIdx.x].first_block, scal->lr_t, s_red); return; }
@@ -2024,6 +2102,7 @@ struct PairWs {
     int nneu, ncbx;     // neutral blocks per row block of the (B,B) launch (0: off); ncbx = ncb + nneu row-sum slabs / loss partials per row block
     float *cpart;       // deterministic step (carve_pair_ws_det; else NULL): [2 * ceil(3B / CH)][d] chunk sums of k_seg_reduce<LPR, true>
     float *wblk;        //   and [nblk_bwd][2*d] per-block branch-vector partial rows of k_pair_bwd_stage<.., true>
+    float *spart;       // deterministic LightGCN step (carve_lgcn_ws; else NULL): [2 * ceil(3B / CH)] chunk sums of the ego branch scalars
     size_t bytes;
 };
 
@@ -2060,7 +2139,7 @@ static PairWs carve_pair_ws(void *base, int B, int d, bool force_staged = false,
     const size_t nsort = 3 * (size_t)B;
     w.ska = w.sva = w.skb = w.svb = nullptr;
     w.perm = w.us = w.is = w.js = nullptr; w.ghist = nullptr; w.stage = nullptr; w.n_work = nullptr;
-    w.cpart = w.wblk = nullptr;
+    w.cpart = w.wblk = w.spart = nullptr;
     if (w.staged) {
         w.ska = static_cast<uint32_t *>(take(nsort * 4)); w.sva = static_cast<uint32_t *>(take(nsort * 4));
         w.skb = static_cast<uint32_t *>(take(nsort * 4)); w.svb = static_cast<uint32_t *>(take(nsort * 4));
@@ -2153,21 +2232,22 @@ static int launch_seg_index(int B, int d, int n_urows, int n_irows, const RefSor
 static int launch_ref_sort_reduce(int B, int d, int n_urows, int n_irows, const int32_t *u, const int32_t *i,
                                   const int32_t *j, float *gU, float *gI, int32_t *tU, int32_t *tI, const PairWs &ws,
                                   hipStream_t st, const uint32_t **sv_sorted = nullptr, const float *sst = nullptr,
-                                  float *sbr = nullptr) {
+                                  float *sbr = nullptr, const uint32_t **sk_sorted = nullptr) {
     const int n = 3 * B;
     const RefSort r = launch_ref_sort(B, n_urows, n_irows, u, i, j, ws, st);
     MACR_CHECK_LAUNCH("ref_sort", st);
+    if (sk_sorted) *sk_sorted = r.sk;             // (the sorted keys stay in the workspace until the next sort)
     if (sv_sorted) {
         *sv_sorted = r.sv;
         return launch_seg_index(B, d, n_urows, n_irows, r, false, gU, gI, tU, tI, ws, st);
     }
     if (ws.cpart) {                       // deterministic step: chunk sums to their own slots, then one owner per row
-        MACR_REQUIRE(!sst, MACR_E_UNSUPPORTED, "pair: the ego branch has no deterministic reduce");
+        MACR_REQUIRE(!sst || (sbr && ws.spart), MACR_E_UNSUPPORTED, "pair: this workspace has no slots for the ego branch scalars");
         MACR_DISPATCH_LPR(d, (k_seg_reduce<LPR, true><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
-                                 n, n_urows, (uint32_t)(n_urows + n_irows), r.sk, r.sv, ws.stage, gU, gI, tU, tI, nullptr, nullptr, ws.cpart)));
+                                 n, n_urows, (uint32_t)(n_urows + n_irows), r.sk, r.sv, ws.stage, gU, gI, tU, tI, sst, sbr, ws.cpart, ws.spart)));
         MACR_CHECK_LAUNCH("seg_reduce", st);
         MACR_DISPATCH_LPR(d, (k_seg_fold<LPR><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
-                                 n, n_urows, (uint32_t)(n_urows + n_irows), r.sk, ws.cpart, gU, gI)));
+                                 n, n_urows, (uint32_t)(n_urows + n_irows), r.sk, ws.cpart, gU, gI, sst ? ws.spart : nullptr, sbr)));
         MACR_CHECK_LAUNCH("seg_fold", st);
         return MACR_OK;
     }
@@ -2188,7 +2268,8 @@ static int launch_pair(int kind, int B, int d, int n_urows, int n_irows, const i
                        const PendingAdam *pa = nullptr, const AdamArgs *pending = nullptr,
                        long long n_pending_blocks = 0, const LossArgs *finalize = nullptr, bool loss_only = false,
                        int32_t *cnt_pos = nullptr, const uint32_t **sv_sorted = nullptr, LazyState *tick = nullptr,
-                       const float *Bsrc = nullptr, float *sbr = nullptr) {
+                       const float *Bsrc = nullptr, float *sbr = nullptr, const uint32_t **sk_sorted = nullptr) {
+    // sk_sorted (deterministic LightGCN step): *sk_sorted = the keys of the sorted reference list, for what follows the reduce
     const int grid = ws.nblk_pair;
     const int user_branch = kind == MACR_LOSS_RUBIBCEBOTH;
     const int rubibpr = kind == MACR_LOSS_RUBIBPR;
@@ -2226,7 +2307,7 @@ static int launch_pair(int kind, int B, int d, int n_urows, int n_irows, const i
                                               adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, listed ? rs.free_val : nullptr))));
             MACR_CHECK_LAUNCH("pair_normal", st);
             if (listed) return launch_seg_index(B, d, n_urows, n_irows, rs, true, gU, gI, tU, tI, ws, st);
-            return launch_ref_sort_reduce(B, d, n_urows, n_irows, u, i, j, gU, gI, tU, tI, ws, st, sv_sorted);
+            return launch_ref_sort_reduce(B, d, n_urows, n_irows, u, i, j, gU, gI, tU, tI, ws, st, sv_sorted, nullptr, nullptr, sk_sorted);
         }
         k_batch_sort<<<(B + kBucketSpan - 1) / kBucketSpan, 256, 0, st>>>(sort);
         MACR_CHECK_LAUNCH("batch_sort", st);
@@ -2262,6 +2343,18 @@ static int launch_pair(int kind, int B, int d, int n_urows, int n_irows, const i
     if (loss_only) return MACR_OK;
     LossArgs L;
     if (finalize) L = *finalize; else L.losses = nullptr;
+    if (ws.staged && ego && ws.wblk) {    // deterministic step: as below, the branch scalars staged like the default step's
+        MACR_REQUIRE(!listed, MACR_E_UNSUPPORTED, "pair: the deterministic step is unfused");
+        float *sst = ws.fwd + 2 * (size_t)ws.Bp - B;
+        MACR_DISPATCH_LPR(d, (k_pair_bwd_stage<LPR, true, false, true><<<ws.nblk_bwd + 1, 256, 0, st>>>(
+                                 B, ws.Bp, ws.nrb, ws.ncb, u, i, j, Usrc, Isrc, w, wu, ws.fwd, ws.rowpart, ws.colpart, ws.stage,
+                                 ws.wblk, hp->alpha, hp->beta, coef, adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, L,
+                                 nullptr, 0, tick, ws.nneu, Bsrc, sst)));
+        MACR_CHECK_LAUNCH("pair_bwd", st);
+        k_branch_fold<<<(kBranchSlots * 2 * d + 255) / 256, 256, 0, st>>>(ws.nblk_bwd, 2 * d, ws.wblk, ws.gw);
+        MACR_CHECK_LAUNCH("branch_fold", st);
+        return launch_ref_sort_reduce(B, d, n_urows, n_irows, u, i, j, gU, gI, tU, tI, ws, st, nullptr, sst, sbr, sk_sorted);
+    }
     if (ws.staged && ego) {
         // the branch scalars are staged over the (B,B) row factors a, b of fwd (read by nothing after the (B,B) launch):
         // sst[r] for the item references r in [B, 3B) is fwd[2 Bp + r - B]
@@ -2275,7 +2368,7 @@ static int launch_pair(int kind, int B, int d, int n_urows, int n_irows, const i
         return launch_ref_sort_reduce(B, d, n_urows, n_irows, u, i, j, gU, gI, tU, tI, ws, st, nullptr, sst, sbr);
     }
     if (ws.staged && ws.wblk) {           // deterministic step: per-block branch-vector rows, folded in block order
-        MACR_REQUIRE(!listed && !ego, MACR_E_UNSUPPORTED, "pair: the deterministic step is unfused and has no ego branch");
+        MACR_REQUIRE(!listed, MACR_E_UNSUPPORTED, "pair: the deterministic step is unfused");
         MACR_DISPATCH_RUBIBPR(MACR_DISPATCH_LPR(d, (k_pair_bwd_stage<LPR, false, RB, true><<<ws.nblk_bwd + 1, 256, 0, st>>>(
                                  B, ws.Bp, ws.nrb, ws.ncb, u, i, j, Usrc, Isrc, w, wu, ws.fwd, ws.rowpart, ws.colpart, ws.stage,
                                  ws.wblk, hp->alpha, hp->beta, coef, adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, L,
@@ -2283,7 +2376,7 @@ static int launch_pair(int kind, int B, int d, int n_urows, int n_irows, const i
         MACR_CHECK_LAUNCH("pair_bwd", st);
         k_branch_fold<<<(kBranchSlots * 2 * d + 255) / 256, 256, 0, st>>>(ws.nblk_bwd, 2 * d, ws.wblk, ws.gw);
         MACR_CHECK_LAUNCH("branch_fold", st);
-        return launch_ref_sort_reduce(B, d, n_urows, n_irows, u, i, j, gU, gI, tU, tI, ws, st, nullptr);
+        return launch_ref_sort_reduce(B, d, n_urows, n_irows, u, i, j, gU, gI, tU, tI, ws, st, nullptr, nullptr, nullptr, sk_sorted);
     }
     if (ws.staged) {
         MACR_DISPATCH_RUBIBPR(MACR_DISPATCH_LPR(d, (k_pair_bwd_stage<LPR, false, RB><<<ws.nblk_bwd + 1, 256, 0, st>>>(
@@ -3124,8 +3217,15 @@ extern "C" int macr_lazy_flush(int d, long long n_rows_p, long long n_rows_q, fl
 // ---- LightGCN ---------------------------------------------------------------
 namespace macr {
 struct PlanHeaderLite { int32_t magic, n_items, n_split, n_slots, N, chunk, n_groups, reserved; };   // = spmm_kernels.hip PlanHeader
-struct LgcnWs { float *E, *dE, *G, *work; int32_t *cnt; double *emb_acc; float *sbr; PairWs pair; size_t bytes; };
-static LgcnWs carve_lgcn_ws(void *base, int B, int N, int d, const PlanHeaderLite *ph, const PlanHeaderLite *pht = nullptr) {
+struct LgcnWs {
+    float *E, *dE, *G, *work; int32_t *cnt; double *emb_acc; float *sbr; PairWs pair;
+    double *epart; int nblk_reg;     // deterministic step (else NULL, 0): the block sums of k_reg_rows
+    size_t bytes;
+};
+// det (MACR_STEP_DETERMINISTIC): the same layout with the pair workspace of carve_pair_ws_det, and behind it the chunk sums of
+// the ego branch scalars (k_seg_reduce<LPR, true>) and the emb_loss block sums -- both rewritten by every step that reads them
+static LgcnWs carve_lgcn_ws(void *base, int B, int N, int d, const PlanHeaderLite *ph, const PlanHeaderLite *pht = nullptr,
+                            bool det = false) {
     LgcnWs w;
     char *p = static_cast<char *>(base);
     const size_t nd = align_up((size_t)N * d * 4, 256);
@@ -3141,8 +3241,15 @@ static LgcnWs carve_lgcn_ws(void *base, int B, int N, int d, const PlanHeaderLit
     w.cnt = static_cast<int32_t *>(take(align_up((size_t)N * 4, 256)));    // references of the current batch per row (zero between steps)
     w.emb_acc = static_cast<double *>(take(kEmbSlots * 8));                 // emb_loss partial sums (zero between steps)
     w.sbr = static_cast<float *>(take(align_up((size_t)N * 4, 256)));      // --loss bce2: branch scalar per ego row (zero between steps)
-    w.pair = carve_pair_ws(p ? p + off : nullptr, B, d);
+    w.pair = det ? carve_pair_ws_det(p ? p + off : nullptr, B, d) : carve_pair_ws(p ? p + off : nullptr, B, d);
     off += w.pair.bytes;
+    w.epart = nullptr; w.nblk_reg = 0;
+    if (det) {
+        const int ch = d / 4 < 16 ? d / 4 : 16, rpb = 256 / (d / 4);       // = CH of k_seg_reduce, rows per block of k_reg_rows
+        w.pair.spart = static_cast<float *>(take(align_up(2 * ((3 * (size_t)B + ch - 1) / ch) * 4, 256)));
+        w.nblk_reg = (int)((3 * (size_t)B + rpb - 1) / rpb);
+        w.epart = static_cast<double *>(take(align_up((size_t)w.nblk_reg * 8, 256)));
+    }
     w.bytes = off;
     return w;
 }
@@ -3157,6 +3264,15 @@ extern "C" size_t macr_lgcn_train_workspace_bytes(int B, int N, int d, const voi
 extern "C" size_t macr_lgcn_train_workspace_bytes_t(int B, int N, int d, const void *plan_host, const void *plan_t_host) {
     if (B <= 0 || N <= 0 || !dim_supported(d)) return 0;
     return carve_lgcn_ws(nullptr, B, N, d, static_cast<const PlanHeaderLite *>(plan_host), static_cast<const PlanHeaderLite *>(plan_t_host)).bytes;
+}
+extern "C" size_t macr_lgcn_train_workspace_bytes_det_t(int B, int N, int d, const void *plan_host, const void *plan_t_host) {
+    if (B <= 0 || N <= 0 || !dim_supported(d)) return 0;
+    const PlanHeaderLite *ph = static_cast<const PlanHeaderLite *>(plan_host), *pht = static_cast<const PlanHeaderLite *>(plan_t_host);
+    const size_t det = carve_lgcn_ws(nullptr, B, N, d, ph, pht, true).bytes, plain = carve_lgcn_ws(nullptr, B, N, d, ph, pht).bytes;
+    return det > plain ? det : plain;
+}
+extern "C" size_t macr_lgcn_train_workspace_bytes_det(int B, int N, int d, const void *plan_host) {
+    return macr_lgcn_train_workspace_bytes_det_t(B, N, d, plan_host, nullptr);
 }
 
 // rowptr_t / col_t / val_t / plan_t_*: the TRANSPOSED adjacency, used by the backward propagation (the gradient of A E is A^T dE:
@@ -3182,8 +3298,12 @@ extern "C" int macr_lgcn_train_step_t(int loss_kind, int B, int d, int n_users, 
     MACR_REQUIRE((plan_t_dev == nullptr) == (plan_t_host == nullptr) && (plan_t_dev == nullptr) == (plan_dev == nullptr), MACR_E_INVALID,
                  "lgcn_train_step: the transposed adjacency comes with a plan when the adjacency does");
     MACR_REQUIRE(w && wu && mw && vw && mwu && vwu, MACR_E_INVALID, "lgcn_train_step: null branch vectors");
-    MACR_REQUIRE((flags & ~(MACR_STEP_LOSS_ONLY | MACR_STEP_DENSE_LAYERS)) == 0, MACR_E_INVALID, "lgcn_train_step: flags=%d", flags);
+    MACR_REQUIRE((flags & ~(MACR_STEP_LOSS_ONLY | MACR_STEP_DENSE_LAYERS | MACR_STEP_DETERMINISTIC)) == 0, MACR_E_INVALID,
+                 "lgcn_train_step: flags=%d", flags);
     const bool loss_only = flags & MACR_STEP_LOSS_ONLY;
+    // the bit-reproducible step (include/macr_hip.h): the pair stage staged and folded at every B, the regulariser and emb_loss
+    // by one owner per row (k_reg_rows), fused epilogues that leave emb_acc alone
+    const bool det = flags & MACR_STEP_DETERMINISTIC;
     if (int e = validate_hyper(hp, "lgcn_train_step")) return e;
     const int N = n_users + n_items;
     MACR_REQUIRE((plan_dev == nullptr) == (plan_host == nullptr), MACR_E_INVALID,
@@ -3192,7 +3312,7 @@ extern "C" int macr_lgcn_train_step_t(int loss_kind, int B, int d, int n_users, 
     MACR_REQUIRE(!ph || ph->N == N, MACR_E_INVALID, "lgcn_train_step: plan does not belong to this graph");
     const PlanHeaderLite *pht = static_cast<const PlanHeaderLite *>(plan_t_host);
     MACR_REQUIRE(!pht || pht->N == N, MACR_E_INVALID, "lgcn_train_step: transposed plan does not belong to this graph");
-    LgcnWs ws = carve_lgcn_ws(workspace, B, N, d, ph, pht == ph ? nullptr : pht);
+    LgcnWs ws = carve_lgcn_ws(workspace, B, N, d, ph, pht == ph ? nullptr : pht, det);
     MACR_REQUIRE(workspace_bytes >= ws.bytes, MACR_E_WORKSPACE, "lgcn_train_step: workspace %zu < %zu bytes",
                  workspace_bytes, ws.bytes);
     MACR_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, MACR_E_INVALID,
@@ -3250,10 +3370,12 @@ extern "C" int macr_lgcn_train_step_t(int loss_kind, int B, int d, int n_users, 
     if (!sparse) fill_words(ws.dE, nd, 0u, st);
     // pair loss on the propagated rows; items live at rows n_users.. of E
     float *Ei = ws.E + (size_t)n_users * d, *dEi = ws.dE + (size_t)n_users * d;
+    const uint32_t *sk = nullptr;                     // deterministic step: the sorted keys of the batch's references
     if (int e = launch_pair(loss_kind, B, d, n_users, n_items, u, i, j, ws.E, Ei, w, wu, ws.dE, dEi, nullptr, nullptr,
                             0.0f, 0, adam_pow, hp, ws.pair, st, nullptr, nullptr, 0, nullptr, false,
-                            sparse && !ws.pair.staged ? ws.cnt + n_users : nullptr, nullptr, nullptr, Ti0, sbr_i))
+                            sparse && !ws.pair.staged ? ws.cnt + n_users : nullptr, nullptr, nullptr, Ti0, sbr_i, det ? &sk : nullptr))
         return e;
+    MACR_REQUIRE(!det || sk, MACR_E_LAUNCH, "lgcn_train_step: the deterministic pair stage left no sorted reference list");
     AdamArgs a;
     a.n_seg = 0;
     a.lpr = d / 4; a.lpr_shift = d == 32 ? 3 : d == 64 ? 4 : d == 128 ? 5 : 6;
@@ -3263,7 +3385,14 @@ extern "C" int macr_lgcn_train_step_t(int loss_kind, int B, int d, int n_users, 
     if (sparse) {
         // backward through the propagation with the optimizer in the last layer's epilogue (spmm_kernels.hip AdamFuse):
         // gradient row + ego-row regulariser (LightGCN.py:525-528) -> Adam on T, no G, no separate pass over the table
-        const AdamFuse fuse = {T, mT, vT, ws.pair.scal, hp->beta1, hp->beta2, hp->adam_eps, coef, ws.dE, ws.emb_acc,
+        if (det) {                                      // emb_loss from T as it is before the fused layer moves it
+            MACR_DISPATCH_LPR(d, (k_reg_rows<LPR><<<ws.nblk_reg, 256, 0, st>>>(3 * B, sk, T, nullptr, coef, ws.epart)));
+            MACR_CHECK_LAUNCH("reg_rows", st);
+            k_emb_fold<<<1, 256, 0, st>>>(ws.nblk_reg, ws.epart, ws.emb_acc, nullptr);
+            MACR_CHECK_LAUNCH("emb_fold", st);
+        }
+        // (deterministic step: emb_acc = NULL selects the epilogues that do not add into it)
+        const AdamFuse fuse = {T, mT, vT, ws.pair.scal, hp->beta1, hp->beta2, hp->adam_eps, coef, ws.dE, det ? nullptr : ws.emb_acc,
                                ego ? ws.sbr : nullptr, w};
         SparseCtx spt = sp;
         spt.chunk = pht ? pht->chunk : 0x7fffffff;
@@ -3285,8 +3414,16 @@ extern "C" int macr_lgcn_train_step_t(int loss_kind, int B, int d, int n_users, 
     // l2 regulariser on the ego rows (LightGCN.py:525-528)
     // (the batch grouped by positive item, as the pair launch left it in the workspace, when there is one)
     const int32_t *gu = ws.pair.staged ? u : ws.pair.us, *gi = ws.pair.staged ? i : ws.pair.is, *gj = ws.pair.staged ? j : ws.pair.js;
-    MACR_DISPATCH_D(d, (k_reg_scatter<D><<<ws.pair.nblk_bwd, 256, 0, st>>>(B, n_users, gu, gi, gj, T, ws.G, coef, ws.pair.part2)));
-    MACR_CHECK_LAUNCH("reg_scatter", st);
+    if (det) {                                          // one owner per row instead of one atomic per reference and element
+        MACR_DISPATCH_LPR(d, (k_reg_rows<LPR><<<ws.nblk_reg, 256, 0, st>>>(3 * B, sk, T, ws.G, coef, ws.epart)));
+        MACR_CHECK_LAUNCH("reg_rows", st);
+        k_emb_fold<<<1, 256, 0, st>>>(ws.nblk_reg, ws.epart, nullptr, ws.pair.part2);
+        MACR_CHECK_LAUNCH("emb_fold", st);
+        L.n_part2 = 1;                                  // (emb_loss: the fold's sum in slot 0 of part2)
+    } else {
+        MACR_DISPATCH_D(d, (k_reg_scatter<D><<<ws.pair.nblk_bwd, 256, 0, st>>>(B, n_users, gu, gi, gj, T, ws.G, coef, ws.pair.part2)));
+        MACR_CHECK_LAUNCH("reg_scatter", st);
+    }
     if (ego) {
         MACR_DISPATCH_LPR(d, (k_ego_branch_rows<LPR><<<(n_items + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
                                  n_items, w, sbr_i, ws.G + (size_t)n_users * d)));

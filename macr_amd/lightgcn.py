@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .mf import Fetch, xavier_uniform
+from .mf import Fetch, deterministic_from_env, xavier_uniform
 
 
 class LightGCN(object):
@@ -33,7 +33,10 @@ class LightGCN(object):
     # the kind of the rubi_ratings2 fetch: SCORE_RUBI with the item branch on the ego rows
     RUBI_EGO = (ops.SCORE_RUBI, "ego")
 
-    def __init__(self, data_config, args, pretrain_data=None, device=None, seed=12345, weights=None):
+    def __init__(self, data_config, args, pretrain_data=None, device=None, seed=12345, weights=None, deterministic=None):
+        """deterministic: every training and loss-only step of every optimizer carries MACR_STEP_DETERMINISTIC -- with the
+        deterministic samplers a seed then pins the run bit for bit.  None: MACR_DETERMINISTIC=1 in the environment decides."""
+        self.deterministic = deterministic_from_env() if deterministic is None else bool(deterministic)
         if pretrain_data is not None:
             raise NotImplementedError("pretrained restore is out of scope")
         if getattr(args, "alg_type", "lightgcn") != "lightgcn":
@@ -100,7 +103,7 @@ class LightGCN(object):
         for loss, (suffix, kind) in self._LOSS.items():
             if kind not in self._ON_DEMAND:
                 self._opt[kind] = ops.LGCNState(T, self.n_users, self.n_items, w, wu, adj, self.n_layers, hyper,
-                                                self.batch_size, adj_t=adj_t)
+                                                self.batch_size, adj_t=adj_t, deterministic=self.deterministic)
             # opt_bce ... ; the BPR graph's plain opt, loss ... (:173-178); reg_loss is tf.constant(0.) (:427, :411)
             for base, role in (("opt", "opt"), ("loss", "loss"), ("mf_loss", "mf_loss"), ("emb_loss", "reg_loss"),
                                ("reg_loss", "zero")):
@@ -136,7 +139,8 @@ class LightGCN(object):
         st = self._opt.get(kind)
         if st is None:
             st = self._opt[kind] = ops.LGCNState(self.T, self.n_users, self.n_items, self.w, self.w_user, self._adj,
-                                                 self.n_layers, self._hyper, self.batch_size, adj_t=self._adj_t)
+                                                 self.n_layers, self._hyper, self.batch_size, adj_t=self._adj_t,
+                                                 deterministic=self.deterministic)
         return st
 
     def to_device_batch(self, users, pos_items, neg_items):

@@ -40,7 +40,7 @@ class Fetch(object):
 
 
 def deterministic_from_env():
-    """MACR_DETERMINISTIC=1 in the environment: the MF training step runs in its bit-reproducible mode
+    """MACR_DETERMINISTIC=1 in the environment: the MF and LightGCN training steps run in their bit-reproducible mode
     (include/macr_hip.h, MACR_STEP_DETERMINISTIC)"""
     return os.environ.get("MACR_DETERMINISTIC", "") == "1"
 

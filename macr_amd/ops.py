@@ -754,10 +754,13 @@ class LGCNState(object):
     """Device state of LightGCN: ego table T=[user_embedding; item_embedding] (LightGCN.py:226-232),
     branch vectors, Adam slots, the `pre` adjacency (utility/load_data.py:112-121)."""
 
-    def __init__(self, T, n_users, n_items, w, wu, adj, n_layers, hyper, batch_cap, adj_t=None):
+    def __init__(self, T, n_users, n_items, w, wu, adj, n_layers, hyper, batch_cap, adj_t=None, deterministic=False):
         """adj_t: the TRANSPOSED adjacency (CSR) of an asymmetric --adj_type (norm / gcmc / mean: D^-1 A); the backward
-        propagation runs on it.  None: the adjacency is symmetric (pre, plain)."""
+        propagation runs on it.  None: the adjacency is symmetric (pre, plain).
+        deterministic: every step, loss-only ones included, carries MACR_STEP_DETERMINISTIC (include/macr_hip.h): losses, T,
+        the branch vectors, all slots and the beta powers are a function of the inputs alone, bit for bit."""
         _require_f32(T=T, w=w, wu=wu)
+        self.deterministic = bool(deterministic)
         self.T = T.contiguous()
         self.n_users, self.n_items, self.n_layers = n_users, n_items, n_layers
         self.w, self.wu = w.reshape(-1).contiguous(), wu.reshape(-1).contiguous()
@@ -774,11 +777,13 @@ class LGCNState(object):
 
     def reserve(self, B):
         if B > self.batch_cap:
+            L = _lib.lib()
             if self.adj_t is None:
-                nbytes = _lib.lib().macr_lgcn_train_workspace_bytes(B, self.T.shape[0], self.d, self.adj._plan_ptrs()[1])
+                size_of = L.macr_lgcn_train_workspace_bytes_det if self.deterministic else L.macr_lgcn_train_workspace_bytes
+                nbytes = size_of(B, self.T.shape[0], self.d, self.adj._plan_ptrs()[1])
             else:
-                nbytes = _lib.lib().macr_lgcn_train_workspace_bytes_t(B, self.T.shape[0], self.d, self.adj._plan_ptrs()[1],
-                                                                      self.adj_t._plan_ptrs()[1])
+                size_of = L.macr_lgcn_train_workspace_bytes_det_t if self.deterministic else L.macr_lgcn_train_workspace_bytes_t
+                nbytes = size_of(B, self.T.shape[0], self.d, self.adj._plan_ptrs()[1], self.adj_t._plan_ptrs()[1])
             if nbytes == 0:
                 raise MacrError(_lib.E_UNSUPPORTED, "embed_size %d not in {32,64,128,256}" % self.d)
             # zero once (include/macr_hip.h): row flags and the hub rows' arrival counters are
@@ -804,7 +809,8 @@ class LGCNState(object):
             _ptr(at.ptr, _i32), _ptr(at.idx, _i32), _ptr(at.val, _f32), ptd, pth, _ptr(u, _i32), _ptr(i, _i32), _ptr(j, _i32),
             _ptr(self.T), _ptr(self.w), _ptr(self.wu), _ptr(self.mT), _ptr(self.vT), _ptr(self.mw), _ptr(self.vw),
             _ptr(self.mwu), _ptr(self.vwu), _ptr(self.adam_pow), ctypes.byref(self.hyper), _ptr(out, _f32),
-            (_lib.STEP_LOSS_ONLY if loss_only else 0) | (_lib.STEP_DENSE_LAYERS if dense_layers else 0), _ptr(self.ws),
+            (_lib.STEP_LOSS_ONLY if loss_only else 0) | (_lib.STEP_DENSE_LAYERS if dense_layers else 0) |
+            (_lib.STEP_DETERMINISTIC if self.deterministic else 0), _ptr(self.ws),
             self.ws.numel(), _stream()))
         return out
 
