@@ -15,6 +15,7 @@
 // cross-lane shuffles.
 #include "common.hpp"
 #include "refsort.hpp"
+#include "spmm.hpp"
 
 #include <type_traits>
 
@@ -1931,34 +1932,10 @@ __global__ __launch_bounds__(256) void k_reg_scatter(int B, int item_off, const 
     if (threadIdx.x == 0) part[(size_t)blockIdx.x * kPartStride] = s0;    // slot 0 only
 }
 
-}  // namespace macr
-
 // ============================================================================
 // Host side: workspace carving + launch sequences (C ABI)
 // ============================================================================
-namespace macr {
-
-struct SparseCtx {                // = spmm_kernels.hip
-    int32_t *cnt;                 // [N] references of the current batch per row (0: not a row of the batch)
-    const int32_t *u, *i, *j;     // the batch: rows u[b], n_users + i[b], n_users + j[b]
-    int B, n_users;
-    int chunk;                    // rows longer than this are hub rows (cut into pieces by the plan); INT_MAX without a plan
-    int count;                    // kSparseOut: 1 = count the references into cnt
-};
-struct AdamFuse {                 // = spmm_kernels.hip: dense Adam on the ego table in the epilogue of the last backward layer
-    float *T, *m, *v;
-    const StepScalars *scal;
-    float b1, b2, eps, coef;
-    float *dE;
-    double *emb_acc;
-    float *sb;
-    const float *bw;
-};
-int launch_propagate(int N, int d, int n_layers, const int32_t *rowptr, const int32_t *col, const float *val,
-                     const void *plan_dev, const void *plan_host_header, const float *E0, float *E, float *work,
-                     hipStream_t st, const SparseCtx *sp, int sparse_mode, const AdamFuse *fuse);   // spmm_kernels.hip
-constexpr int kSparseOut = 1, kSparseIn = 2;                                          // = spmm_kernels.hip
-constexpr int kEmbSlots = 2048;
+constexpr int kEmbSlots = 2048;       // slots of AdamFuse::emb_acc (spmm.hpp)
 
 // The tail of a fused LightGCN step: Adam on the branch vectors (their gradients are the partial rows pair_bwd left) and
 // the losses -- emb_loss from the sums of cnt * |T row|^2 the fused epilogue accumulated (cleared here for the next step).
@@ -2168,31 +2145,42 @@ static PairWs carve_pair_ws_det(void *base, int B, int d) {
 }
 
 // grid: nbxb (B,B) blocks, then the blocks that group the batch (small path), then the pending Adam blocks
-template <int R, int CELL = kCellBce>
-static void launch_bxb_rows(const PairWs &ws, int B, const AdamArgs *pending, long long n_adam_blocks,
+// nbxb: every row block (ws.nrb * ws.ncb), or a rank's row blocks [rb0, rb1) of the row-sharded step: (rb1 - rb0) * ws.ncb
+// with sort.rb0 = rb0
+template <int CELL = kCellBce>
+static void launch_bxb_rows(const PairWs &ws, int B, int nbxb, const AdamArgs *pending, long long n_adam_blocks,
                             const BatchSort &sort, hipStream_t st) {
-    const int nbxb = ws.ncb * ws.nrb, nsort = (sort.B + kBucketSpan - 1) / kBucketSpan + sort.nneu * ws.nrb;    // (+ the neutral blocks)
+    const int nsort = (sort.B + kBucketSpan - 1) / kBucketSpan + sort.nneu * ws.nrb;    // (+ the neutral blocks)
     const bool full = B % 256 == 0;
 #ifdef MACR_ABL_XNOADAM
     n_adam_blocks = 0;                 // timing probe: the ADAM instantiation of the kernel without any Adam block (wrong results)
 #endif
-    if (pending && pending->lazy) {
-        const unsigned grid = (unsigned)(nbxb + nsort + n_adam_blocks);
-        if (full) k_bxb<R, true, 2, CELL><<<grid, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, *pending, ws.scal, sort);
-        else      k_bxb<R, false, 2, CELL><<<grid, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, *pending, ws.scal, sort);
-    } else if (pending) {
-        const unsigned grid = (unsigned)(nbxb + nsort + n_adam_blocks);
-        if (full) k_bxb<R, true, 1, CELL><<<grid, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, *pending, ws.scal, sort);
-        else      k_bxb<R, false, 1, CELL><<<grid, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, *pending, ws.scal, sort);
-    } else {
-        AdamArgs none;
-        none.n_seg = 0;
-        if (full) k_bxb<R, true, 0, CELL><<<nbxb + nsort, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, none, ws.scal, sort);
-        else      k_bxb<R, false, 0, CELL><<<nbxb + nsort, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, none, ws.scal, sort);
+    auto launch = [&](auto rows) {                 // rows: std::integral_constant<int, R>
+        constexpr int R = decltype(rows)::value;
+        if (pending && pending->lazy) {
+            const unsigned grid = (unsigned)(nbxb + nsort + n_adam_blocks);
+            if (full) k_bxb<R, true, 2, CELL><<<grid, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, *pending, ws.scal, sort);
+            else      k_bxb<R, false, 2, CELL><<<grid, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, *pending, ws.scal, sort);
+        } else if (pending) {
+            const unsigned grid = (unsigned)(nbxb + nsort + n_adam_blocks);
+            if (full) k_bxb<R, true, 1, CELL><<<grid, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, *pending, ws.scal, sort);
+            else      k_bxb<R, false, 1, CELL><<<grid, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, *pending, ws.scal, sort);
+        } else {
+            AdamArgs none;
+            none.n_seg = 0;
+            if (full) k_bxb<R, true, 0, CELL><<<nbxb + nsort, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, none, ws.scal, sort);
+            else      k_bxb<R, false, 0, CELL><<<nbxb + nsort, 256, 0, st>>>(B, ws.Bp, ws.ncb, nbxb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, none, ws.scal, sort);
+        }
+    };
+    switch (ws.rows) {
+        case 1: launch(std::integral_constant<int, 1>()); break;
+        case 2: launch(std::integral_constant<int, 2>()); break;
+        default: launch(std::integral_constant<int, 4>()); break;
     }
 }
 
-static BatchSort batch_sort_args(const PairWs &ws, int B, const int32_t *u, const int32_t *i, const int32_t *j) {
+static BatchSort batch_sort_args(const PairWs &ws, int B = 0, const int32_t *u = nullptr, const int32_t *i = nullptr,
+                                 const int32_t *j = nullptr) {      // (no arguments: no batch to group)
     BatchSort s;
     s.u = u; s.i = i; s.j = j; s.B = B; s.rb0 = 0;
     s.perm = ws.perm; s.us = ws.us; s.is = ws.is; s.js = ws.js;
@@ -2200,19 +2188,18 @@ static BatchSort batch_sort_args(const PairWs &ws, int B, const int32_t *u, cons
     return s;
 }
 
-// staged path: sort the 3B references by row, then one owner per row sums its staging rows into gU/gI
-// sv_sorted != NULL: INDEX mode -- rows whose references lie in one chunk get a flag naming them instead of a sum
-// (*sv_sorted = the sorted list's values, for the indexed Adam pass that must follow)
+// staged path: the 3B references sorted by row
 struct RefSort { const uint32_t *sk, *sv; uint32_t *free_key, *free_val; };
-static RefSort launch_ref_sort(int B, int n_urows, int n_irows, const int32_t *u, const int32_t *i, const int32_t *j,
-                               const PairWs &ws, hipStream_t st) {
-    const int n = 3 * B;
-    k_refs_init<<<(B + 255) / 256 < 2048 ? (B + 255) / 256 : 2048, 256, 0, st>>>(B, n_urows, u, i, j, ws.ska, ws.sva, ws.n_work);
-    const int flip = launch_radix_sort(ws.ska, ws.sva, ws.skb, ws.svb, n, (uint32_t)(n_urows + n_irows - 1), ws.ghist, st);
+static RefSort ref_sort_result(const PairWs &ws, int flip) {      // flip: what launch_radix_sort returned
     RefSort r;
     r.sk = flip ? ws.skb : ws.ska; r.sv = flip ? ws.svb : ws.sva;
     r.free_key = flip ? ws.ska : ws.skb; r.free_val = flip ? ws.sva : ws.svb;     // the buffers the sort no longer needs
     return r;
+}
+static RefSort launch_ref_sort(int B, int n_urows, int n_irows, const int32_t *u, const int32_t *i, const int32_t *j,
+                               const PairWs &ws, hipStream_t st) {
+    k_refs_init<<<(B + 255) / 256 < 2048 ? (B + 255) / 256 : 2048, 256, 0, st>>>(B, n_urows, u, i, j, ws.ska, ws.sva, ws.n_work);
+    return ref_sort_result(ws, launch_radix_sort(ws.ska, ws.sva, ws.skb, ws.svb, 3 * B, (uint32_t)(n_urows + n_irows - 1), ws.ghist, st));
 }
 // place[reference] = its position in the sorted list (the inverse of the list's values)
 __global__ __launch_bounds__(256) void k_ref_place(int n, const uint32_t *__restrict__ sv, uint32_t *__restrict__ place) {
@@ -2229,60 +2216,91 @@ static int launch_seg_index(int B, int d, int n_urows, int n_irows, const RefSor
     MACR_CHECK_LAUNCH("seg_sum", st);
     return MACR_OK;
 }
-static int launch_ref_sort_reduce(int B, int d, int n_urows, int n_irows, const int32_t *u, const int32_t *i,
-                                  const int32_t *j, float *gU, float *gI, int32_t *tU, int32_t *tI, const PairWs &ws,
-                                  hipStream_t st, const uint32_t **sv_sorted = nullptr, const float *sst = nullptr,
-                                  float *sbr = nullptr, const uint32_t **sk_sorted = nullptr) {
+// the sum behind a sort, every row written: one owner per row sums its staging rows into gU/gI and flags the row (sst, sbr:
+// the staged ego branch scalars summed into the rows' scalars alongside)
+static int launch_seg_reduce(int B, int d, int n_urows, int n_irows, const RefSort &r, float *gU, float *gI, int32_t *tU,
+                             int32_t *tI, const float *sst, float *sbr, const PairWs &ws, hipStream_t st) {
     const int n = 3 * B;
-    const RefSort r = launch_ref_sort(B, n_urows, n_irows, u, i, j, ws, st);
-    MACR_CHECK_LAUNCH("ref_sort", st);
-    if (sk_sorted) *sk_sorted = r.sk;             // (the sorted keys stay in the workspace until the next sort)
-    if (sv_sorted) {
-        *sv_sorted = r.sv;
-        return launch_seg_index(B, d, n_urows, n_irows, r, false, gU, gI, tU, tI, ws, st);
-    }
-    if (ws.cpart) {                       // deterministic step: chunk sums to their own slots, then one owner per row
-        MACR_REQUIRE(!sst || (sbr && ws.spart), MACR_E_UNSUPPORTED, "pair: this workspace has no slots for the ego branch scalars");
-        MACR_DISPATCH_LPR(d, (k_seg_reduce<LPR, true><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
-                                 n, n_urows, (uint32_t)(n_urows + n_irows), r.sk, r.sv, ws.stage, gU, gI, tU, tI, sst, sbr, ws.cpart, ws.spart)));
-        MACR_CHECK_LAUNCH("seg_reduce", st);
-        MACR_DISPATCH_LPR(d, (k_seg_fold<LPR><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
-                                 n, n_urows, (uint32_t)(n_urows + n_irows), r.sk, ws.cpart, gU, gI, sst ? ws.spart : nullptr, sbr)));
-        MACR_CHECK_LAUNCH("seg_fold", st);
-        return MACR_OK;
-    }
     MACR_DISPATCH_LPR(d, (k_seg_reduce<LPR><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
                              n, n_urows, (uint32_t)(n_urows + n_irows), r.sk, r.sv, ws.stage, gU, gI, tU, tI, sst, sbr)));
     MACR_CHECK_LAUNCH("seg_reduce", st);
     return MACR_OK;
 }
 
-// forward + (B,B) + backward of the pair loss; on return (stream order) gU/gI hold the de-duplicated gradient rows.
-// n_urows / n_irows: rows of the tables Usrc / Isrc (sort key range).
-// Bsrc, sbr (MACR_LOSS_RUBIBCE_EGO): the item rows of the branch logits and the item rows' branch scalars (zero on entry;
-// sbr[row] = the sum of d mf_loss / d s over the row's references on return, in stream order)
-static int launch_pair(int kind, int B, int d, int n_urows, int n_irows, const int32_t *u, const int32_t *i,
-                       const int32_t *j, const float *Usrc, const float *Isrc, const float *w, const float *wu,
-                       float *gU, float *gI, int32_t *tU, int32_t *tI, float coef, int reg_on_gathered,
-                       float *adam_pow, const macr_hyper *hp, const PairWs &ws, hipStream_t st,
-                       const PendingAdam *pa = nullptr, const AdamArgs *pending = nullptr,
-                       long long n_pending_blocks = 0, const LossArgs *finalize = nullptr, bool loss_only = false,
-                       int32_t *cnt_pos = nullptr, const uint32_t **sv_sorted = nullptr, LazyState *tick = nullptr,
-                       const float *Bsrc = nullptr, float *sbr = nullptr, const uint32_t **sk_sorted = nullptr) {
-    // sk_sorted (deterministic LightGCN step): *sk_sorted = the keys of the sorted reference list, for what follows the reduce
-    const int grid = ws.nblk_pair;
+// What launch_pair runs: forward + (B,B) + backward of the pair loss of one batch.  A caller names the members it means.
+struct PairCall {
+    int kind = 0, B = 0, d = 0;                   // MACR_LOSS_*, triples of the batch, floats per row
+    int n_urows = 0, n_irows = 0;                 // rows of the tables Usrc / Isrc (sort key range)
+    const int32_t *u = nullptr, *i = nullptr, *j = nullptr;      // the batch: user, positive and negative row of every triple
+    const float *Usrc = nullptr, *Isrc = nullptr; // the tables the batch's rows are read from
+    const float *w = nullptr, *wu = nullptr;      // branch vectors of the item and the user branch
+    float *gU = nullptr, *gI = nullptr;           // on return (stream order): the de-duplicated gradient rows
+    int32_t *tU = nullptr, *tI = nullptr;         // row flags of gU / gI for the Adam pass (NULL: none kept)
+    float coef = 0.f;                             // d reg / d row = decay / batch_size (0: the caller adds the regulariser)
+    int reg_on_gathered = 0;                      // 1: the regulariser and its loss are taken on the rows of Usrc / Isrc
+    float *adam_pow = nullptr;                    // the two beta powers; the backward kernel derives lr_t and advances them
+    const macr_hyper *hp = nullptr;
+    // deferred / lazy MF step
+    const PendingAdam *pa = nullptr;              // the previous step's dense pass is pending: pair_fwd looks one update ahead
+    const AdamArgs *pending = nullptr;            //   and the pass itself rides in the (B,B) launch,
+    long long n_pending_blocks = 0;               //   in that many blocks
+    const LossArgs *finalize = nullptr;           // the backward kernel's last block writes the losses (no Adam pass follows)
+    LazyState *tick = nullptr;                    // lazy Adam: the backward kernel's last block advances the step counter
+    // indexed staging
+    const uint32_t **sv_sorted = nullptr;         // the Adam pass follows at once: INDEX mode, *sv_sorted = the sorted list's values (or NULL)
+    // LightGCN
+    bool loss_only = false;                       // forward only: the loss partials, no gradient
+    int32_t *cnt_pos = nullptr;                   // small path: the references per positive item row are counted into it
+    const float *Bsrc = nullptr;                  // MACR_LOSS_RUBIBCE_EGO: the item rows of the branch logits
+    float *sbr = nullptr;                         //   and the item rows' branch scalars: zero on entry, += d mf_loss / d s per reference
+    const uint32_t **sk_sorted = nullptr;         // deterministic step: *sk_sorted = the keys of the sorted reference list
+};
+
+// staged path: sort the 3B references by row, then one owner per row sums its staging rows into gU/gI
+// sv_sorted != NULL: INDEX mode -- rows whose references lie in one chunk get a flag naming them instead of a sum
+// (*sv_sorted = the sorted list's values, for the indexed Adam pass that must follow).  sst != NULL: with the ego branch scalars
+static int launch_ref_sort_reduce(const PairCall &c, const uint32_t **sv_sorted, const float *sst, const PairWs &ws,
+                                  hipStream_t st) {
+    const int B = c.B, d = c.d, n_urows = c.n_urows, n_irows = c.n_irows, n = 3 * B;
+    float *sbr = sst ? c.sbr : nullptr;
+    const RefSort r = launch_ref_sort(B, n_urows, n_irows, c.u, c.i, c.j, ws, st);
+    MACR_CHECK_LAUNCH("ref_sort", st);
+    if (c.sk_sorted) *c.sk_sorted = r.sk;         // (the sorted keys stay in the workspace until the next sort)
+    if (sv_sorted) {
+        *sv_sorted = r.sv;
+        return launch_seg_index(B, d, n_urows, n_irows, r, false, c.gU, c.gI, c.tU, c.tI, ws, st);
+    }
+    if (ws.cpart) {                       // deterministic step: chunk sums to their own slots, then one owner per row
+        MACR_REQUIRE(!sst || (sbr && ws.spart), MACR_E_UNSUPPORTED, "pair: this workspace has no slots for the ego branch scalars");
+        MACR_DISPATCH_LPR(d, (k_seg_reduce<LPR, true><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
+                                 n, n_urows, (uint32_t)(n_urows + n_irows), r.sk, r.sv, ws.stage, c.gU, c.gI, c.tU, c.tI, sst, sbr, ws.cpart, ws.spart)));
+        MACR_CHECK_LAUNCH("seg_reduce", st);
+        MACR_DISPATCH_LPR(d, (k_seg_fold<LPR><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
+                                 n, n_urows, (uint32_t)(n_urows + n_irows), r.sk, ws.cpart, c.gU, c.gI, sst ? ws.spart : nullptr, sbr)));
+        MACR_CHECK_LAUNCH("seg_fold", st);
+        return MACR_OK;
+    }
+    return launch_seg_reduce(B, d, n_urows, n_irows, r, c.gU, c.gI, c.tU, c.tI, sst, sbr, ws, st);
+}
+
+// forward + (B,B) + backward of the pair loss; on return (stream order) c.gU / c.gI hold the de-duplicated gradient rows
+static int launch_pair(const PairCall &c, const PairWs &ws, hipStream_t st) {
+    const int kind = c.kind, B = c.B, d = c.d;
+    const macr_hyper *hp = c.hp;
     const int user_branch = kind == MACR_LOSS_RUBIBCEBOTH;
     const int rubibpr = kind == MACR_LOSS_RUBIBPR;
-    const bool ego = Bsrc != nullptr;
+    const bool ego = c.Bsrc != nullptr;
     MACR_REQUIRE(!rubibpr || (ws.nneu == 0 && !ego), MACR_E_INVALID, "pair: the BPR cell has no neutral blocks and no ego branch");
-    BatchSort sort = batch_sort_args(ws, B, u, i, j);
-    if (ws.staged || loss_only) sort.B = 0;
+    BatchSort sort = batch_sort_args(ws, B, c.u, c.i, c.j);
+    if (ws.staged || c.loss_only) sort.B = 0;
     sort.outflag = ws.fwd + 6 * (size_t)ws.Bp; sort.nneu = ws.nneu; sort.ncbx = ws.ncbx;      // neutralised columns of the (B,B) launch (pair_fwd flags them)
-    if (is_pair_loss(kind) && loss_only) {                    // forward of the per-pair loss, nothing written but partials
+    if (is_pair_loss(kind) && c.loss_only) {                    // forward of the per-pair loss, nothing written but partials
         const int nb = (B + kChunkT - 1) / kChunkT < 1024 ? (B + kChunkT - 1) / kChunkT : 1024;
+        float *const no_rows = nullptr;
+        int32_t *const no_flags = nullptr;
         MACR_DISPATCH_PAIR_LOSS(kind, MACR_DISPATCH_D(d, (k_pair_normal<PL, D><<<nb, 256, 0, st>>>(
-                                              B, u, i, j, Usrc, Isrc, nullptr, nullptr, nullptr, nullptr, ws.part, coef,
-                                              reg_on_gathered, adam_pow, nullptr, ws.scal, hp->lr, hp->beta1, hp->beta2, nullptr))));
+                                              B, c.u, c.i, c.j, c.Usrc, c.Isrc, no_rows, no_rows, no_flags, no_flags, ws.part, c.coef,
+                                              c.reg_on_gathered, c.adam_pow, nullptr, ws.scal, hp->lr, hp->beta1, hp->beta2, nullptr))));
         MACR_CHECK_LAUNCH("pair_normal", st);
         return MACR_OK;
     }
@@ -2291,113 +2309,91 @@ static int launch_pair(int kind, int B, int d, int n_urows, int n_irows, const i
     // reads a row's <= 16 staging rows as one run (805 MB of scattered 256-byte reads at B = 2^20 became sequential) and
     // needs no list to find them.  MACR_STAGE_LISTED=0: staging in batch order, found through the list (before round 4).
     static const bool listed_ok = !(getenv("MACR_STAGE_LISTED") && atoi(getenv("MACR_STAGE_LISTED")) == 0);
-    const bool listed = ws.staged && sv_sorted && listed_ok && !loss_only;
+    const bool listed = ws.staged && c.sv_sorted && listed_ok && !c.loss_only;
     RefSort rs = {};
     if (listed) {
-        rs = launch_ref_sort(B, n_urows, n_irows, u, i, j, ws, st);
+        rs = launch_ref_sort(B, c.n_urows, c.n_irows, c.u, c.i, c.j, ws, st);
         MACR_CHECK_LAUNCH("ref_sort", st);
         k_ref_place<<<(3 * B + 255) / 256 < 4096 ? (3 * B + 255) / 256 : 4096, 256, 0, st>>>(3 * B, rs.sv, rs.free_val);
         MACR_CHECK_LAUNCH("ref_place", st);
-        *sv_sorted = nullptr;                                    // (the indexed pass finds the rows by position)
+        *c.sv_sorted = nullptr;                                  // (the indexed pass finds the rows by position)
     }
     if (is_pair_loss(kind)) {
         if (ws.staged) {
             MACR_DISPATCH_PAIR_LOSS(kind, MACR_DISPATCH_LPR(d, (k_pair_normal_stage<PL, LPR><<<ws.nblk_bwd, 256, 0, st>>>(
-                                              B, u, i, j, Usrc, Isrc, ws.stage, ws.part, coef, reg_on_gathered, adam_pow,
-                                              adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, listed ? rs.free_val : nullptr))));
+                                              B, c.u, c.i, c.j, c.Usrc, c.Isrc, ws.stage, ws.part, c.coef, c.reg_on_gathered, c.adam_pow,
+                                              c.adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, listed ? rs.free_val : nullptr))));
             MACR_CHECK_LAUNCH("pair_normal", st);
-            if (listed) return launch_seg_index(B, d, n_urows, n_irows, rs, true, gU, gI, tU, tI, ws, st);
-            return launch_ref_sort_reduce(B, d, n_urows, n_irows, u, i, j, gU, gI, tU, tI, ws, st, sv_sorted, nullptr, nullptr, sk_sorted);
+            if (listed) return launch_seg_index(B, d, c.n_urows, c.n_irows, rs, true, c.gU, c.gI, c.tU, c.tI, ws, st);
+            return launch_ref_sort_reduce(c, c.sv_sorted, nullptr, ws, st);
         }
         k_batch_sort<<<(B + kBucketSpan - 1) / kBucketSpan, 256, 0, st>>>(sort);
         MACR_CHECK_LAUNCH("batch_sort", st);
         MACR_DISPATCH_PAIR_LOSS(kind, MACR_DISPATCH_D(d, (k_pair_normal<PL, D><<<ws.nblk_bwd, 256, 0, st>>>(
-                                              B, ws.us, ws.is, ws.js, Usrc, Isrc, gU, gI, tU, tI, ws.part, coef, reg_on_gathered,
-                                              adam_pow, adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, cnt_pos))));
+                                              B, ws.us, ws.is, ws.js, c.Usrc, c.Isrc, c.gU, c.gI, c.tU, c.tI, ws.part, c.coef, c.reg_on_gathered,
+                                              c.adam_pow, c.adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, c.cnt_pos))));
         MACR_CHECK_LAUNCH("pair_normal", st);
         return MACR_OK;
     }
     // RB: the kernels' template flag of MACR_LOSS_RUBIBPR (one argument list per launch, both values of the flag)
 #define MACR_DISPATCH_RUBIBPR(...)                                          \
     if (rubibpr) { constexpr bool RB = true; __VA_ARGS__; } else { constexpr bool RB = false; __VA_ARGS__; }
-    if (pa && pa->lazy) {
-        MACR_DISPATCH_RUBIBPR(MACR_DISPATCH_LPR(d, (k_pair_fwd<LPR, 2, RB><<<grid, 256, 0, st>>>(B, ws.Bp, u, i, j, Usrc, Isrc, w, wu, ws.fwd,
-                                                                                            ws.part, reg_on_gathered, ws.gw, *pa, user_branch))));
-    } else if (pa) {
-        MACR_DISPATCH_RUBIBPR(MACR_DISPATCH_LPR(d, (k_pair_fwd<LPR, 1, RB><<<grid, 256, 0, st>>>(B, ws.Bp, u, i, j, Usrc, Isrc, w, wu, ws.fwd,
-                                                                                            ws.part, reg_on_gathered, ws.gw, *pa, user_branch))));
+    if (c.pa && c.pa->lazy) {
+        MACR_DISPATCH_RUBIBPR(MACR_DISPATCH_LPR(d, (k_pair_fwd<LPR, 2, RB><<<ws.nblk_pair, 256, 0, st>>>(B, ws.Bp, c.u, c.i, c.j, c.Usrc, c.Isrc, c.w, c.wu, ws.fwd,
+                                                                                            ws.part, c.reg_on_gathered, ws.gw, *c.pa, user_branch))));
+    } else if (c.pa) {
+        MACR_DISPATCH_RUBIBPR(MACR_DISPATCH_LPR(d, (k_pair_fwd<LPR, 1, RB><<<ws.nblk_pair, 256, 0, st>>>(B, ws.Bp, c.u, c.i, c.j, c.Usrc, c.Isrc, c.w, c.wu, ws.fwd,
+                                                                                            ws.part, c.reg_on_gathered, ws.gw, *c.pa, user_branch))));
     } else {
         PendingAdam none = {};
-        MACR_DISPATCH_RUBIBPR(MACR_DISPATCH_LPR(d, (k_pair_fwd<LPR, 0, RB><<<grid, 256, 0, st>>>(B, ws.Bp, u, i, j, Usrc, Isrc, w, wu, ws.fwd,
-                                                                                            ws.part, reg_on_gathered, ws.gw, none, user_branch, Bsrc))));
+        MACR_DISPATCH_RUBIBPR(MACR_DISPATCH_LPR(d, (k_pair_fwd<LPR, 0, RB><<<ws.nblk_pair, 256, 0, st>>>(B, ws.Bp, c.u, c.i, c.j, c.Usrc, c.Isrc, c.w, c.wu, ws.fwd,
+                                                                                            ws.part, c.reg_on_gathered, ws.gw, none, user_branch, c.Bsrc))));
     }
     MACR_CHECK_LAUNCH("pair_fwd", st);
-    MACR_DISPATCH_RUBIBPR(
-        constexpr int CELL = RB ? kCellBpr : kCellBce;
-        switch (ws.rows) {
-            case 1: launch_bxb_rows<1, CELL>(ws, B, pending, n_pending_blocks, sort, st); break;
-            case 2: launch_bxb_rows<2, CELL>(ws, B, pending, n_pending_blocks, sort, st); break;
-            default: launch_bxb_rows<4, CELL>(ws, B, pending, n_pending_blocks, sort, st); break;
-        });
-    MACR_CHECK_LAUNCH(pending ? "bxb+adam" : "bxb", st);
-    if (loss_only) return MACR_OK;
+    MACR_DISPATCH_RUBIBPR(launch_bxb_rows<RB ? kCellBpr : kCellBce>(ws, B, ws.nrb * ws.ncb, c.pending, c.n_pending_blocks, sort, st));
+    MACR_CHECK_LAUNCH(c.pending ? "bxb+adam" : "bxb", st);
+    if (c.loss_only) return MACR_OK;
     LossArgs L;
-    if (finalize) L = *finalize; else L.losses = nullptr;
-    if (ws.staged && ego && ws.wblk) {    // deterministic step: as below, the branch scalars staged like the default step's
-        MACR_REQUIRE(!listed, MACR_E_UNSUPPORTED, "pair: the deterministic step is unfused");
-        float *sst = ws.fwd + 2 * (size_t)ws.Bp - B;
-        MACR_DISPATCH_LPR(d, (k_pair_bwd_stage<LPR, true, false, true><<<ws.nblk_bwd + 1, 256, 0, st>>>(
-                                 B, ws.Bp, ws.nrb, ws.ncb, u, i, j, Usrc, Isrc, w, wu, ws.fwd, ws.rowpart, ws.colpart, ws.stage,
-                                 ws.wblk, hp->alpha, hp->beta, coef, adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, L,
-                                 nullptr, 0, tick, ws.nneu, Bsrc, sst)));
-        MACR_CHECK_LAUNCH("pair_bwd", st);
-        k_branch_fold<<<(kBranchSlots * 2 * d + 255) / 256, 256, 0, st>>>(ws.nblk_bwd, 2 * d, ws.wblk, ws.gw);
-        MACR_CHECK_LAUNCH("branch_fold", st);
-        return launch_ref_sort_reduce(B, d, n_urows, n_irows, u, i, j, gU, gI, tU, tI, ws, st, nullptr, sst, sbr, sk_sorted);
-    }
-    if (ws.staged && ego) {
-        // the branch scalars are staged over the (B,B) row factors a, b of fwd (read by nothing after the (B,B) launch):
-        // sst[r] for the item references r in [B, 3B) is fwd[2 Bp + r - B]
-        MACR_REQUIRE(!listed, MACR_E_UNSUPPORTED, "pair: the ego branch has no indexed staging");
-        float *sst = ws.fwd + 2 * (size_t)ws.Bp - B;
-        MACR_DISPATCH_LPR(d, (k_pair_bwd_stage<LPR, true><<<ws.nblk_bwd + 1, 256, 0, st>>>(
-                                 B, ws.Bp, ws.nrb, ws.ncb, u, i, j, Usrc, Isrc, w, wu, ws.fwd, ws.rowpart, ws.colpart, ws.stage,
-                                 ws.gw, hp->alpha, hp->beta, coef, adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, L,
-                                 nullptr, 0, tick, ws.nneu, Bsrc, sst)));
-        MACR_CHECK_LAUNCH("pair_bwd", st);
-        return launch_ref_sort_reduce(B, d, n_urows, n_irows, u, i, j, gU, gI, tU, tI, ws, st, nullptr, sst, sbr);
-    }
-    if (ws.staged && ws.wblk) {           // deterministic step: per-block branch-vector rows, folded in block order
-        MACR_REQUIRE(!listed, MACR_E_UNSUPPORTED, "pair: the deterministic step is unfused");
-        MACR_DISPATCH_RUBIBPR(MACR_DISPATCH_LPR(d, (k_pair_bwd_stage<LPR, false, RB, true><<<ws.nblk_bwd + 1, 256, 0, st>>>(
-                                 B, ws.Bp, ws.nrb, ws.ncb, u, i, j, Usrc, Isrc, w, wu, ws.fwd, ws.rowpart, ws.colpart, ws.stage,
-                                 ws.wblk, hp->alpha, hp->beta, coef, adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, L,
-                                 nullptr, 0, tick, ws.nneu))));
-        MACR_CHECK_LAUNCH("pair_bwd", st);
-        k_branch_fold<<<(kBranchSlots * 2 * d + 255) / 256, 256, 0, st>>>(ws.nblk_bwd, 2 * d, ws.wblk, ws.gw);
-        MACR_CHECK_LAUNCH("branch_fold", st);
-        return launch_ref_sort_reduce(B, d, n_urows, n_irows, u, i, j, gU, gI, tU, tI, ws, st, nullptr, nullptr, nullptr, sk_sorted);
-    }
+    if (c.finalize) L = *c.finalize; else L.losses = nullptr;
     if (ws.staged) {
-        MACR_DISPATCH_RUBIBPR(MACR_DISPATCH_LPR(d, (k_pair_bwd_stage<LPR, false, RB><<<ws.nblk_bwd + 1, 256, 0, st>>>(
-                                 B, ws.Bp, ws.nrb, ws.ncb, u, i, j, Usrc, Isrc, w, wu, ws.fwd, ws.rowpart, ws.colpart, ws.stage,
-                                 ws.gw, hp->alpha, hp->beta, coef, adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, L,
-                                 listed ? rs.free_val : nullptr, 0, tick, ws.nneu))));
+        const bool det = ws.wblk != nullptr;  // deterministic step: per-block branch-vector rows, folded in block order
+        if (det) MACR_REQUIRE(!listed, MACR_E_UNSUPPORTED, "pair: the deterministic step is unfused");
+        if (ego) MACR_REQUIRE(!listed, MACR_E_UNSUPPORTED, "pair: the ego branch has no indexed staging");
+        // ego: the branch scalars are staged over the (B,B) row factors a, b of fwd (read by nothing after the (B,B) launch):
+        // sst[r] for the item references r in [B, 3B) is fwd[2 Bp + r - B]
+        float *sst = ego ? ws.fwd + 2 * (size_t)ws.Bp - B : nullptr;
+        float *wpart = det ? ws.wblk : ws.gw;
+        // (no EGO && RB instantiation: that pair was refused on entry)
+#define MACR_PAIR_BWD_STAGE(EGO, RB, DET)                                                                                             \
+        MACR_DISPATCH_LPR(d, (k_pair_bwd_stage<LPR, EGO, RB, DET><<<ws.nblk_bwd + 1, 256, 0, st>>>(                                   \
+                                 B, ws.Bp, ws.nrb, ws.ncb, c.u, c.i, c.j, c.Usrc, c.Isrc, c.w, c.wu, ws.fwd, ws.rowpart, ws.colpart,  \
+                                 ws.stage, wpart, hp->alpha, hp->beta, c.coef, c.adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, L,  \
+                                 listed ? rs.free_val : nullptr, 0, c.tick, ws.nneu, c.Bsrc, sst)))
+        if (ego && det) { MACR_PAIR_BWD_STAGE(true, false, true); }
+        else if (ego) { MACR_PAIR_BWD_STAGE(true, false, false); }
+        else if (det) { MACR_DISPATCH_RUBIBPR(MACR_PAIR_BWD_STAGE(false, RB, true)); }
+        else { MACR_DISPATCH_RUBIBPR(MACR_PAIR_BWD_STAGE(false, RB, false)); }
+#undef MACR_PAIR_BWD_STAGE
         MACR_CHECK_LAUNCH("pair_bwd", st);
-        if (listed) return launch_seg_index(B, d, n_urows, n_irows, rs, true, gU, gI, tU, tI, ws, st);
-        return launch_ref_sort_reduce(B, d, n_urows, n_irows, u, i, j, gU, gI, tU, tI, ws, st, sv_sorted);
+        if (det) {
+            k_branch_fold<<<(kBranchSlots * 2 * d + 255) / 256, 256, 0, st>>>(ws.nblk_bwd, 2 * d, ws.wblk, ws.gw);
+            MACR_CHECK_LAUNCH("branch_fold", st);
+        }
+        if (listed) return launch_seg_index(B, d, c.n_urows, c.n_irows, rs, true, c.gU, c.gI, c.tU, c.tI, ws, st);
+        // (the deterministic and the ego reduce write every row: no INDEX mode behind them)
+        return launch_ref_sort_reduce(c, det || ego ? nullptr : c.sv_sorted, sst, ws, st);
     }
     if (ego) {
         MACR_DISPATCH_D(d, (k_pair_bwd<D, true><<<ws.nblk_bwd + 1, 256, 0, st>>>(B, ws.Bp, ws.nrb, ws.ncb, ws.perm, ws.us, ws.is, ws.js,
-                                                                            Usrc, Isrc, w, wu, ws.fwd, ws.rowpart, ws.colpart, gU,
-                                                                            gI, tU, tI, ws.gw, hp->alpha, hp->beta, coef, adam_pow,
-                                                                            ws.scal, hp->lr, hp->beta1, hp->beta2, L, cnt_pos, tick,
-                                                                            ws.nneu, Bsrc, sbr)));
+                                                                            c.Usrc, c.Isrc, c.w, c.wu, ws.fwd, ws.rowpart, ws.colpart, c.gU,
+                                                                            c.gI, c.tU, c.tI, ws.gw, hp->alpha, hp->beta, c.coef, c.adam_pow,
+                                                                            ws.scal, hp->lr, hp->beta1, hp->beta2, L, c.cnt_pos, c.tick,
+                                                                            ws.nneu, c.Bsrc, c.sbr)));
     } else {
         MACR_DISPATCH_RUBIBPR(MACR_DISPATCH_D(d, (k_pair_bwd<D, false, RB><<<ws.nblk_bwd + 1, 256, 0, st>>>(
-                                 B, ws.Bp, ws.nrb, ws.ncb, ws.perm, ws.us, ws.is, ws.js, Usrc, Isrc, w, wu, ws.fwd, ws.rowpart, ws.colpart, gU,
-                                 gI, tU, tI, ws.gw, hp->alpha, hp->beta, coef, adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, L, cnt_pos,
-                                 tick, ws.nneu))));
+                                 B, ws.Bp, ws.nrb, ws.ncb, ws.perm, ws.us, ws.is, ws.js, c.Usrc, c.Isrc, c.w, c.wu, ws.fwd, ws.rowpart, ws.colpart, c.gU,
+                                 c.gI, c.tU, c.tI, ws.gw, hp->alpha, hp->beta, c.coef, c.adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, L, c.cnt_pos,
+                                 c.tick, ws.nneu))));
     }
 #undef MACR_DISPATCH_RUBIBPR
     MACR_CHECK_LAUNCH("pair_bwd", st);
@@ -2415,12 +2411,38 @@ static void add_seg(AdamArgs &a, float *theta, float *m, float *v, float *g, int
     next_block += (s.n_vec + kAdamVecPerBlock - 1) / kAdamVecPerBlock;
 }
 
-static int validate_lazy(const macr_lazy_adam *lz, bool need_p, bool need_q, const char *who);
+// an empty segment list for rows of d floats
+static void adam_args_begin(AdamArgs &a, int d, const macr_hyper *hp) {
+    a.n_seg = 0;
+    a.lpr = d / 4; a.lpr_shift = d == 32 ? 3 : d == 64 ? 4 : d == 128 ? 5 : 6;
+    a.b1 = hp->beta1; a.b2 = hp->beta2; a.eps = hp->adam_eps;
+}
+// the branch vectors (their gradients: the partial rows gw of pair_bwd) as the loss kind trains them (model.py:74 / :69 / :95)
+static void add_branch_segs(AdamArgs &a, int loss_kind, int d, float *w, float *mw, float *vw, float *wu, float *mwu, float *vwu,
+                            float *gw, long long &nb) {
+    // w: both branch losses; w_user: rubibceboth only (its gradient is None elsewhere -> TF leaves it alone)
+    if (!is_pair_loss(loss_kind)) add_seg(a, w, mw, vw, gw, nullptr, 1, nb, kBranchSlots, 2 * d);
+    if (loss_kind == MACR_LOSS_RUBIBCEBOTH) add_seg(a, wu, mwu, vwu, gw + d, nullptr, 1, nb, kBranchSlots, 2 * d);
+}
+// the fields of LossArgs every step fills alike (the callers set their partial arrays and counts)
+static LossArgs loss_args(int kind, int B, const macr_hyper *hp, float *losses) {
+    LossArgs L;
+    L.kind = kind; L.B = B; L.batch_size_cfg = hp->batch_size_cfg;
+    L.alpha = hp->alpha; L.beta = hp->beta; L.decay = hp->decay; L.losses = losses;
+    return L;
+}
+
 static int validate_hyper(const macr_hyper *hp, const char *who) {
     MACR_REQUIRE(hp, MACR_E_INVALID, "%s: hyper is null", who);
     MACR_REQUIRE(hp->batch_size_cfg > 0, MACR_E_INVALID, "%s: batch_size_cfg=%d", who, hp->batch_size_cfg);
     MACR_REQUIRE(hp->beta1 > 0.f && hp->beta1 < 1.f && hp->beta2 > 0.f && hp->beta2 < 1.f, MACR_E_INVALID,
                  "%s: adam betas (%g,%g) outside (0,1)", who, hp->beta1, hp->beta2);
+    return MACR_OK;
+}
+static int validate_lazy(const macr_lazy_adam *lz, bool need_p, bool need_q, const char *who) {
+    MACR_REQUIRE(lz->state && (lz->stampP || !need_p) && (lz->stampQ || !need_q), MACR_E_INVALID, "%s: lazy: null pointer", who);
+    MACR_REQUIRE(lz->period >= 1 && lz->period <= MACR_LAZY_MAX_PERIOD, MACR_E_INVALID, "%s: lazy period %d outside [1, %d]", who,
+                 lz->period, MACR_LAZY_MAX_PERIOD);
     return MACR_OK;
 }
 
@@ -2446,21 +2468,15 @@ static void mf_adam_args(AdamArgs &a, long long &nb, bool tables, int loss_kind,
                          float *P, float *Q, float *w, float *wu, float *mP, float *vP, float *mQ, float *vQ,
                          float *mw, float *vw, float *mwu, float *vwu, float *gP, float *gQ, int32_t *tP,
                          int32_t *tQ, const macr_hyper *hp, const PairWs &ws) {
-    a.n_seg = 0;
-    a.lpr = d / 4; a.lpr_shift = d == 32 ? 3 : d == 64 ? 4 : d == 128 ? 5 : 6;
-    a.b1 = hp->beta1; a.b2 = hp->beta2; a.eps = hp->adam_eps;
+    adam_args_begin(a, d, hp);
     nb = 0;
     if (tables) {
         add_seg(a, P, mP, vP, gP, tP, n_users, nb);
         add_seg(a, Q, mQ, vQ, gQ, tQ, n_items, nb);
     }
-    // w: both branch losses; w_user: rubibceboth only (its gradient is None elsewhere -> TF leaves it alone)
-    if (!is_pair_loss(loss_kind)) add_seg(a, w, mw, vw, ws.gw, nullptr, 1, nb, kBranchSlots, 2 * d);
-    if (loss_kind == MACR_LOSS_RUBIBCEBOTH) add_seg(a, wu, mwu, vwu, ws.gw + d, nullptr, 1, nb, kBranchSlots, 2 * d);
+    add_branch_segs(a, loss_kind, d, w, mw, vw, wu, mwu, vwu, ws.gw, nb);
 }
-}  // namespace macr
 
-namespace macr {
 // lazy dense Adam on the tables of the MF model: stamps of the segments, the ring, the period
 static void lazy_adam_args(AdamArgs &a, const macr_lazy_adam *lz, const float *P) {
     a.lazy = static_cast<const LazyState *>(lz->state);
@@ -2473,8 +2489,7 @@ static int lazy_flush_tables(int d, long long n_rows_p, long long n_rows_q, floa
                              float *vQ, const macr_hyper *hp, const macr_lazy_adam *lazy, hipStream_t st) {
     AdamArgs a;
     long long nb = 0;
-    a.n_seg = 0; a.lpr = d / 4; a.lpr_shift = d == 32 ? 3 : d == 64 ? 4 : d == 128 ? 5 : 6;
-    a.b1 = hp->beta1; a.b2 = hp->beta2; a.eps = hp->adam_eps;
+    adam_args_begin(a, d, hp);
     if (n_rows_p) { add_seg(a, P, mP, vP, nullptr, nullptr, n_rows_p, nb); a.seg[a.n_seg - 1].stamp = lazy->stampP; }
     if (n_rows_q) { add_seg(a, Q, mQ, vQ, nullptr, nullptr, n_rows_q, nb); a.seg[a.n_seg - 1].stamp = lazy->stampQ; }
     if (a.n_seg == 0) return MACR_OK;
@@ -2522,12 +2537,10 @@ static int mf_train_step(int loss_kind, int B, int d, int n_users, int n_items, 
     hipStream_t st = as_stream(stream);
     const float coef = hp->decay / (float)hp->batch_size_cfg;       // d reg / d row  (model.py:219-221)
     const bool rubi = !is_pair_loss(loss_kind);                  // the (B,B) losses: rubibceboth, rubibce, rubi (BPR)
-    LossArgs L;
+    LossArgs L = loss_args(loss_kind, B, hp, losses);
     L.part = ws.part; L.n_part = rubi ? ws.nblk_pair : ws.nblk_bwd;
     L.part2 = nullptr; L.n_part2 = 0;
     L.lpart = ws.lpart; L.n_lpart = rubi ? ws.nrb * ws.ncbx : 0;
-    L.kind = loss_kind; L.B = B; L.batch_size_cfg = hp->batch_size_cfg;
-    L.alpha = hp->alpha; L.beta = hp->beta; L.decay = hp->decay; L.losses = losses;
     AdamArgs a;
     long long nb = 0;
     const bool pending = flags & MACR_STEP_PENDING, defer = flags & MACR_STEP_DEFER;
@@ -2551,10 +2564,16 @@ static int mf_train_step(int loss_kind, int B, int d, int n_users, int n_items, 
     const char *unfused = getenv("MACR_SEG_UNFUSED");
     const bool indexed = ws.staged && !det && !flags && !lz && (size_t)3 * B <= kRefMaxRefs && !(unfused && unfused[0] == '1');
     const uint32_t *sv_sorted = nullptr;
-    if (int e = launch_pair(loss_kind, B, d, n_users, n_items, u, i, j, P, Q, w, wu, gP, gQ, touchedP, touchedQ, coef, 1,
-                            adam_pow, hp, ws, st, pending ? &pa : nullptr, pending ? &a : nullptr, nb, defer ? &L : nullptr,
-                            false, nullptr, indexed ? &sv_sorted : nullptr, lz ? static_cast<LazyState *>(lz->state) : nullptr))
-        return e;
+    PairCall c;
+    c.kind = loss_kind; c.B = B; c.d = d; c.n_urows = n_users; c.n_irows = n_items;
+    c.u = u; c.i = i; c.j = j; c.Usrc = P; c.Isrc = Q; c.w = w; c.wu = wu;
+    c.gU = gP; c.gI = gQ; c.tU = touchedP; c.tI = touchedQ;
+    c.coef = coef; c.reg_on_gathered = 1; c.adam_pow = adam_pow; c.hp = hp;
+    if (pending) { c.pa = &pa; c.pending = &a; c.n_pending_blocks = nb; }
+    if (defer) c.finalize = &L;
+    if (lz) c.tick = static_cast<LazyState *>(lz->state);
+    if (indexed) c.sv_sorted = &sv_sorted;
+    if (int e = launch_pair(c, ws, st)) return e;
     if (defer) return MACR_OK;
     mf_adam_args(a, nb, true, loss_kind, d, n_users, n_items, P, Q, w, wu, mP, vP, mQ, vQ, mw, vw, mwu, vwu, gP, gQ,
                  touchedP, touchedQ, hp, ws);
@@ -2819,7 +2838,6 @@ static ShardWs carve_shard_ws(void *base, int B, int d) {
     return w;
 }
 static inline int grid_for(long long n) { const long long g = (n + 255) / 256; return (int)(g < 4096 ? (g > 0 ? g : 1) : 4096); }
-}  // namespace macr
 
 #define MACR_SHARD_COMMON(who)                                                                                         \
     MACR_REQUIRE(B > 0 && dim_supported(d), B > 0 ? MACR_E_UNSUPPORTED : MACR_E_INVALID, who ": B=%d d=%d", B, d);      \
@@ -2829,18 +2847,6 @@ static inline int grid_for(long long n) { const long long g = (n + 255) / 256; r
     const PairWs &ws = sw.pair;                                                                                        \
     hipStream_t st = as_stream(stream)
 
-extern "C" size_t macr_shard_workspace_bytes(int B, int d) {
-    if (B <= 0 || !dim_supported(d)) return 0;
-    return carve_shard_ws(nullptr, B, d).bytes;
-}
-
-namespace macr {
-static int validate_lazy(const macr_lazy_adam *lz, bool need_p, bool need_q, const char *who) {
-    MACR_REQUIRE(lz->state && (lz->stampP || !need_p) && (lz->stampQ || !need_q), MACR_E_INVALID, "%s: lazy: null pointer", who);
-    MACR_REQUIRE(lz->period >= 1 && lz->period <= MACR_LAZY_MAX_PERIOD, MACR_E_INVALID, "%s: lazy period %d outside [1, %d]", who,
-                 lz->period, MACR_LAZY_MAX_PERIOD);
-    return MACR_OK;
-}
 static int shard_gather(int B, int d, const float *P_loc, const float *mP, const float *vP, int u_lo, int u_stride, int n_users_loc,
                         const float *Q_loc, const float *mQ, const float *vQ, int i_lo, int i_stride, int n_items_loc,
                         const int32_t *u, const int32_t *i, const int32_t *j, const macr_hyper *hp, const macr_lazy_adam *lz,
@@ -2852,22 +2858,27 @@ static int shard_gather(int B, int d, const float *P_loc, const float *mP, const
     const Owned ou = {u_lo, u_stride, n_users_loc}, oi = {i_lo, i_stride, n_items_loc};
     LazyTable tp = {P_loc, mP, vP, nullptr}, tq = {Q_loc, mQ, vQ, nullptr};
     const int grid = grid_for(3LL * B * (d / 4));
+    const LazyState *state = nullptr;
+    float b1 = 0.f, b2 = 0.f, eps = 0.f;               // (read by the lazy form only)
     if (lz) {
         MACR_REQUIRE(((mP && vP) || n_users_loc == 0) && ((mQ && vQ) || n_items_loc == 0) && hp, MACR_E_INVALID,
                      "shard_gather_lazy: null pointer");
         if (int e = validate_lazy(lz, n_users_loc > 0, n_items_loc > 0, "shard_gather_lazy")) return e;
         tp.stamp = lz->stampP; tq.stamp = lz->stampQ;
-        MACR_DISPATCH_LPR(d, (k_rows_gather_owned<LPR, true><<<grid, 256, 0, as_stream(stream)>>>(
-                                 B, tp, ou, tq, oi, u, i, j, rows3, static_cast<const LazyState *>(lz->state), hp->beta1, hp->beta2,
-                                 hp->adam_eps)));
+        state = static_cast<const LazyState *>(lz->state); b1 = hp->beta1; b2 = hp->beta2; eps = hp->adam_eps;
+        MACR_DISPATCH_LPR(d, (k_rows_gather_owned<LPR, true><<<grid, 256, 0, as_stream(stream)>>>(B, tp, ou, tq, oi, u, i, j, rows3, state, b1, b2, eps)));
     } else {
-        MACR_DISPATCH_LPR(d, (k_rows_gather_owned<LPR, false><<<grid, 256, 0, as_stream(stream)>>>(B, tp, ou, tq, oi, u, i, j, rows3,
-                                                                                                    nullptr, 0.f, 0.f, 0.f)));
+        MACR_DISPATCH_LPR(d, (k_rows_gather_owned<LPR, false><<<grid, 256, 0, as_stream(stream)>>>(B, tp, ou, tq, oi, u, i, j, rows3, state, b1, b2, eps)));
     }
     MACR_CHECK_LAUNCH("shard_gather", as_stream(stream));
     return MACR_OK;
 }
 }  // namespace macr
+
+extern "C" size_t macr_shard_workspace_bytes(int B, int d) {
+    if (B <= 0 || !dim_supported(d)) return 0;
+    return carve_shard_ws(nullptr, B, d).bytes;
+}
 
 extern "C" int macr_shard_gather(int B, int d, const float *P_loc, int u_lo, int u_stride, int n_users_loc, const float *Q_loc,
                                  int i_lo, int i_stride, int n_items_loc, const int32_t *u, const int32_t *i, const int32_t *j,
@@ -2928,16 +2939,9 @@ extern "C" int macr_shard_bxb(int B, int d, int rank, int world, void **partials
     if (partial_bytes) *partial_bytes = (size_t)(hi - lo);
     const int rb0 = (int)((long long)ws.nrb * rank / world), rb1 = (int)((long long)ws.nrb * (rank + 1) / world);
     if (rb1 > rb0) {
-        BatchSort sort = batch_sort_args(ws, 0, nullptr, nullptr, nullptr);
+        BatchSort sort = batch_sort_args(ws);
         sort.rb0 = rb0;
-        const int nb = (rb1 - rb0) * ws.ncb;
-        const bool full = B % 256 == 0;
-        AdamArgs none; none.n_seg = 0;
-#define MACR_BXB_ROWS_LAUNCH(R)                                                                                               \
-        if (full) k_bxb<R, true, 0><<<nb, 256, 0, st>>>(B, ws.Bp, ws.ncb, nb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, none, ws.scal, sort); \
-        else      k_bxb<R, false, 0><<<nb, 256, 0, st>>>(B, ws.Bp, ws.ncb, nb, ws.fwd, ws.rowpart, ws.colpart, ws.lpart, none, ws.scal, sort)
-        switch (ws.rows) { case 1: MACR_BXB_ROWS_LAUNCH(1); break; case 2: MACR_BXB_ROWS_LAUNCH(2); break; default: MACR_BXB_ROWS_LAUNCH(4); break; }
-#undef MACR_BXB_ROWS_LAUNCH
+        launch_bxb_rows(ws, B, (rb1 - rb0) * ws.ncb, nullptr, 0, sort, st);
     }
     MACR_CHECK_LAUNCH("bxb", st);
     return MACR_OK;
@@ -2953,11 +2957,9 @@ extern "C" int macr_shard_backward(int loss_kind, int B, int d, const float *row
     MACR_REQUIRE(rows3 && w && wu && adam_pow && losses, MACR_E_INVALID, "shard_backward: null pointer");
     if (int e = validate_hyper(hp, "shard_backward")) return e;
     MACR_SHARD_COMMON("shard_backward");
-    LossArgs L;
+    LossArgs L = loss_args(loss_kind, B, hp, losses);
     L.part = ws.part; L.n_part = ws.nblk_pair; L.part2 = nullptr; L.n_part2 = 0;
     L.lpart = ws.lpart; L.n_lpart = ws.nrb * ws.ncbx;
-    L.kind = loss_kind; L.B = B; L.batch_size_cfg = hp->batch_size_cfg;
-    L.alpha = hp->alpha; L.beta = hp->beta; L.decay = hp->decay; L.losses = losses;
     const float coef = hp->decay / (float)hp->batch_size_cfg;
     const float *Isrc = rows3 + (size_t)B * d;
     if (is_pair_loss(loss_kind)) {
@@ -3065,11 +3067,9 @@ extern "C" int macr_shard_backward_slice(int loss_kind, int B, int d, int t0, in
                  MACR_E_INVALID, "shard_backward_slice: bad argument");
     if (int e = validate_hyper(hp, "shard_backward_slice")) return e;
     MACR_SHARD_COMMON("shard_backward_slice");
-    LossArgs L;
+    LossArgs L = loss_args(loss_kind, B, hp, losses);
     L.part = ws.part; L.n_part = ws.nblk_pair; L.part2 = nullptr; L.n_part2 = 0;      // (every rank's blocks were summed index by index)
     L.lpart = ws.lpart; L.n_lpart = ws.nrb * ws.ncbx;
-    L.kind = loss_kind; L.B = B; L.batch_size_cfg = hp->batch_size_cfg;
-    L.alpha = hp->alpha; L.beta = hp->beta; L.decay = hp->decay; L.losses = losses;
     const float coef = hp->decay / (float)hp->batch_size_cfg;
     const int lpr = d / 4, rpb = 256 / lpr;
     int nblk = (n + rpb - 1) / rpb;
@@ -3116,38 +3116,27 @@ static int shard_apply(int loss_kind, int B, int d, int n_users_loc, int n_items
     const Owned ou = {u_lo, u_stride, n_users_loc}, oi = {i_lo, i_stride, n_items_loc};
     k_shard_keys<<<grid_for(B), 256, 0, st>>>(B, ou, oi, u, i, j, ws.ska, ws.sva, ws.n_work,
                                               lz ? static_cast<LazyState *>(lz->state) : nullptr, ws.scal);
-    const int flip = launch_radix_sort(ws.ska, ws.sva, ws.skb, ws.svb, n, (uint32_t)(n_users_loc + n_items_loc), ws.ghist, st);
+    const RefSort r = ref_sort_result(ws, launch_radix_sort(ws.ska, ws.sva, ws.skb, ws.svb, n, (uint32_t)(n_users_loc + n_items_loc), ws.ghist, st));
     MACR_CHECK_LAUNCH("ref_sort", st);
-    const uint32_t *sk = flip ? ws.skb : ws.ska, *sv = flip ? ws.svb : ws.sva;
     // The step completes here, so nothing needs a row's gradient as a row in memory: k_seg_scan finds each row's first
     // reference and names its run in the row's flag, the Adam pass sums the <= 16 staged rows itself (adam_block INDEXED;
     // longer runs -- the hot items -- go through gP/gQ by k_seg_sum).  MACR_SEG_UNFUSED=1: the segment reduce writes
     // every row, as before (A/B measurements, tests).
     const char *unfused = getenv("MACR_SEG_UNFUSED");
     const bool indexed = (size_t)n <= kRefMaxRefs && !(unfused && unfused[0] == '1');
-    if (indexed) {
-        uint32_t *work = flip ? ws.ska : ws.skb;                       // the buffer the sort no longer needs
-        k_seg_scan<<<(n + 255) / 256, 256, 0, st>>>(n, n_users_loc, (uint32_t)(n_users_loc + n_items_loc), sk, touchedP, touchedQ, work, ws.n_work);
-        MACR_CHECK_LAUNCH("seg_index", st);
-        MACR_DISPATCH_LPR(d, (k_seg_sum<LPR><<<1024, 256, 0, st>>>(work, ws.n_work, n_users_loc, sk, sv, ws.stage, gP, gQ)));
-        MACR_CHECK_LAUNCH("seg_sum", st);
-    } else {
-        MACR_DISPATCH_LPR(d, (k_seg_reduce<LPR><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
-                                 n, n_users_loc, (uint32_t)(n_users_loc + n_items_loc), sk, sv, ws.stage, gP, gQ, touchedP, touchedQ)));
-        MACR_CHECK_LAUNCH("seg_reduce", st);
-    }
+    if (int e = indexed ? launch_seg_index(B, d, n_users_loc, n_items_loc, r, false, gP, gQ, touchedP, touchedQ, ws, st)
+                        : launch_seg_reduce(B, d, n_users_loc, n_items_loc, r, gP, gQ, touchedP, touchedQ, nullptr, nullptr, ws, st))
+        return e;
     AdamArgs a;
     long long nb = 0;
-    a.n_seg = 0; a.lpr = d / 4; a.lpr_shift = d == 32 ? 3 : d == 64 ? 4 : d == 128 ? 5 : 6;
-    a.b1 = hp->beta1; a.b2 = hp->beta2; a.eps = hp->adam_eps;
+    adam_args_begin(a, d, hp);
     if (n_users_loc) add_seg(a, P, mP, vP, gP, touchedP, n_users_loc, nb);
     if (n_items_loc) add_seg(a, Q, mQ, vQ, gQ, touchedQ, n_items_loc, nb);
     const int n_tab = a.n_seg;
-    if (!is_pair_loss(loss_kind)) add_seg(a, w, mw, vw, ws.gw, nullptr, 1, nb, kBranchSlots, 2 * d);
-    if (loss_kind == MACR_LOSS_RUBIBCEBOTH) add_seg(a, wu, mwu, vwu, ws.gw + d, nullptr, 1, nb, kBranchSlots, 2 * d);
+    add_branch_segs(a, loss_kind, d, w, mw, vw, wu, mwu, vwu, ws.gw, nb);
     LossArgs L; L.losses = nullptr;
     if (indexed)
-        for (int k = 0; k < n_tab; ++k) { a.seg[k].sv = sv; a.seg[k].stage = ws.stage; }
+        for (int k = 0; k < n_tab; ++k) { a.seg[k].sv = r.sv; a.seg[k].stage = ws.stage; }
     if (lz) {
         // (a rank without user rows has its item rows in segment 0: the list's keys are [0, n_users_loc) | [n_users_loc, end) either way)
         LazyArgs z;
@@ -3165,7 +3154,7 @@ static int shard_apply(int loss_kind, int B, int d, int n_users_loc, int n_items
         z.branch_first = at;
         at += a.n_seg - n_tab;
         z.n_refs = n; z.n_users = n_users_loc; z.item_seg = n_users_loc ? 1 : 0;
-        z.key_end = (uint32_t)(n_users_loc + n_items_loc); z.sk = sk;
+        z.key_end = (uint32_t)(n_users_loc + n_items_loc); z.sk = r.sk;
         if (indexed) k_adam_lazy<true, true><<<(unsigned)at, 256, 0, st>>>(a, z, ws.scal);
         else         k_adam_lazy<false, true><<<(unsigned)at, 256, 0, st>>>(a, z, ws.scal);
         MACR_CHECK_LAUNCH("adam_lazy", st);
@@ -3216,7 +3205,6 @@ extern "C" int macr_lazy_flush(int d, long long n_rows_p, long long n_rows_q, fl
 
 // ---- LightGCN ---------------------------------------------------------------
 namespace macr {
-struct PlanHeaderLite { int32_t magic, n_items, n_split, n_slots, N, chunk, n_groups, reserved; };   // = spmm_kernels.hip PlanHeader
 struct LgcnWs {
     float *E, *dE, *G, *work; int32_t *cnt; double *emb_acc; float *sbr; PairWs pair;
     double *epart; int nblk_reg;     // deterministic step (else NULL, 0): the block sums of k_reg_rows
@@ -3224,7 +3212,7 @@ struct LgcnWs {
 };
 // det (MACR_STEP_DETERMINISTIC): the same layout with the pair workspace of carve_pair_ws_det, and behind it the chunk sums of
 // the ego branch scalars (k_seg_reduce<LPR, true>) and the emb_loss block sums -- both rewritten by every step that reads them
-static LgcnWs carve_lgcn_ws(void *base, int B, int N, int d, const PlanHeaderLite *ph, const PlanHeaderLite *pht = nullptr,
+static LgcnWs carve_lgcn_ws(void *base, int B, int N, int d, const PlanHeader *ph, const PlanHeader *pht = nullptr,
                             bool det = false) {
     LgcnWs w;
     char *p = static_cast<char *>(base);
@@ -3257,17 +3245,15 @@ static LgcnWs carve_lgcn_ws(void *base, int B, int N, int d, const PlanHeaderLit
 
 
 extern "C" size_t macr_lgcn_train_workspace_bytes(int B, int N, int d, const void *plan_host) {
-    if (B <= 0 || N <= 0 || !dim_supported(d)) return 0;
-    const PlanHeaderLite *ph = static_cast<const PlanHeaderLite *>(plan_host);
-    return carve_lgcn_ws(nullptr, B, N, d, ph).bytes;
+    return macr_lgcn_train_workspace_bytes_t(B, N, d, plan_host, nullptr);
 }
 extern "C" size_t macr_lgcn_train_workspace_bytes_t(int B, int N, int d, const void *plan_host, const void *plan_t_host) {
     if (B <= 0 || N <= 0 || !dim_supported(d)) return 0;
-    return carve_lgcn_ws(nullptr, B, N, d, static_cast<const PlanHeaderLite *>(plan_host), static_cast<const PlanHeaderLite *>(plan_t_host)).bytes;
+    return carve_lgcn_ws(nullptr, B, N, d, static_cast<const PlanHeader *>(plan_host), static_cast<const PlanHeader *>(plan_t_host)).bytes;
 }
 extern "C" size_t macr_lgcn_train_workspace_bytes_det_t(int B, int N, int d, const void *plan_host, const void *plan_t_host) {
     if (B <= 0 || N <= 0 || !dim_supported(d)) return 0;
-    const PlanHeaderLite *ph = static_cast<const PlanHeaderLite *>(plan_host), *pht = static_cast<const PlanHeaderLite *>(plan_t_host);
+    const PlanHeader *ph = static_cast<const PlanHeader *>(plan_host), *pht = static_cast<const PlanHeader *>(plan_t_host);
     const size_t det = carve_lgcn_ws(nullptr, B, N, d, ph, pht, true).bytes, plain = carve_lgcn_ws(nullptr, B, N, d, ph, pht).bytes;
     return det > plain ? det : plain;
 }
@@ -3308,9 +3294,9 @@ extern "C" int macr_lgcn_train_step_t(int loss_kind, int B, int d, int n_users, 
     const int N = n_users + n_items;
     MACR_REQUIRE((plan_dev == nullptr) == (plan_host == nullptr), MACR_E_INVALID,
                  "lgcn_train_step: plan needs both its device copy and its host copy (or neither)");
-    const PlanHeaderLite *ph = static_cast<const PlanHeaderLite *>(plan_host);
+    const PlanHeader *ph = static_cast<const PlanHeader *>(plan_host);
     MACR_REQUIRE(!ph || ph->N == N, MACR_E_INVALID, "lgcn_train_step: plan does not belong to this graph");
-    const PlanHeaderLite *pht = static_cast<const PlanHeaderLite *>(plan_t_host);
+    const PlanHeader *pht = static_cast<const PlanHeader *>(plan_t_host);
     MACR_REQUIRE(!pht || pht->N == N, MACR_E_INVALID, "lgcn_train_step: transposed plan does not belong to this graph");
     LgcnWs ws = carve_lgcn_ws(workspace, B, N, d, ph, pht == ph ? nullptr : pht, det);
     MACR_REQUIRE(workspace_bytes >= ws.bytes, MACR_E_WORKSPACE, "lgcn_train_step: workspace %zu < %zu bytes",
@@ -3337,25 +3323,25 @@ extern "C" int macr_lgcn_train_step_t(int loss_kind, int B, int d, int n_users, 
     if (int e = launch_propagate(N, d, n_layers, rowptr, col, val, plan_dev, plan_host, T, ws.E, ws.work, st,
                                  sparse ? &sp : nullptr, kSparseOut, nullptr))
         return e;
-    LossArgs L;
+    LossArgs L = loss_args(loss_kind, B, hp, losses);
     L.part = ws.pair.part;
     L.part2 = ws.pair.part2; L.n_part2 = ws.pair.nblk_bwd;
     L.lpart = ws.pair.lpart; L.n_lpart = is_pair_loss(loss_kind) ? 0 : ws.pair.nrb * ws.pair.ncbx;
     // --loss bce2 (LightGCN.py:463-493): the branch logits read the EGO item rows; their gradient reaches those rows directly,
     // as one scalar per row (ws.sbr) times w, added where the ego-row regulariser enters (fused epilogue / G), not through dE
     const bool ego = loss_kind == MACR_LOSS_RUBIBCE_EGO;
-    const float *Ti0 = ego ? T + (size_t)n_users * d : nullptr;
     float *sbr_i = ego ? ws.sbr + n_users : nullptr;
-    L.kind = loss_kind; L.B = B; L.batch_size_cfg = hp->batch_size_cfg;
-    L.alpha = hp->alpha; L.beta = hp->beta; L.decay = hp->decay; L.losses = losses;
     const float coef = hp->decay / (float)hp->batch_size_cfg;
+    // pair loss on the propagated rows; items live at rows n_users.. of E.  (coef = 0: the regulariser is on the EGO rows, below)
+    PairCall c;
+    c.kind = loss_kind; c.B = B; c.d = d; c.n_urows = n_users; c.n_irows = n_items;
+    c.u = u; c.i = i; c.j = j; c.Usrc = ws.E; c.Isrc = ws.E + (size_t)n_users * d; c.w = w; c.wu = wu;
+    c.adam_pow = adam_pow; c.hp = hp;
+    if (ego) c.Bsrc = T + (size_t)n_users * d;
     if (loss_only) {
         // the reference's "test loss" pass (LightGCN.py:799-819): loss_X, mf_loss_X, emb_loss_X without opt_X
-        float *Ei0 = ws.E + (size_t)n_users * d;
-        if (int e = launch_pair(loss_kind, B, d, n_users, n_items, u, i, j, ws.E, Ei0, w, wu, nullptr, nullptr, nullptr,
-                                nullptr, 0.0f, 0, adam_pow, hp, ws.pair, st, nullptr, nullptr, 0, nullptr, true, nullptr, nullptr,
-                                nullptr, Ti0, nullptr))
-            return e;
+        c.loss_only = true;
+        if (int e = launch_pair(c, ws.pair, st)) return e;
         MACR_DISPATCH_D(d, (k_reg_scatter<D><<<ws.pair.nblk_bwd, 256, 0, st>>>(B, n_users, u, i, j, T, nullptr, coef, ws.pair.part2)));
         MACR_CHECK_LAUNCH("reg_scatter", st);
         L.n_part = is_pair_loss(loss_kind)
@@ -3368,18 +3354,15 @@ extern "C" int macr_lgcn_train_step_t(int loss_kind, int B, int d, int n_users, 
     // whole buffer is cleared here (and again on return); sparse layers: every row is zero already (the fused epilogue of the
     // previous step cleared the batch's rows, the workspace starts zeroed).
     if (!sparse) fill_words(ws.dE, nd, 0u, st);
-    // pair loss on the propagated rows; items live at rows n_users.. of E
-    float *Ei = ws.E + (size_t)n_users * d, *dEi = ws.dE + (size_t)n_users * d;
     const uint32_t *sk = nullptr;                     // deterministic step: the sorted keys of the batch's references
-    if (int e = launch_pair(loss_kind, B, d, n_users, n_items, u, i, j, ws.E, Ei, w, wu, ws.dE, dEi, nullptr, nullptr,
-                            0.0f, 0, adam_pow, hp, ws.pair, st, nullptr, nullptr, 0, nullptr, false,
-                            sparse && !ws.pair.staged ? ws.cnt + n_users : nullptr, nullptr, nullptr, Ti0, sbr_i, det ? &sk : nullptr))
-        return e;
+    c.gU = ws.dE; c.gI = ws.dE + (size_t)n_users * d;
+    if (sparse && !ws.pair.staged) c.cnt_pos = ws.cnt + n_users;
+    c.sbr = sbr_i;
+    if (det) c.sk_sorted = &sk;
+    if (int e = launch_pair(c, ws.pair, st)) return e;
     MACR_REQUIRE(!det || sk, MACR_E_LAUNCH, "lgcn_train_step: the deterministic pair stage left no sorted reference list");
     AdamArgs a;
-    a.n_seg = 0;
-    a.lpr = d / 4; a.lpr_shift = d == 32 ? 3 : d == 64 ? 4 : d == 128 ? 5 : 6;
-    a.b1 = hp->beta1; a.b2 = hp->beta2; a.eps = hp->adam_eps;
+    adam_args_begin(a, d, hp);
     long long nb = 0;
     L.n_part = is_pair_loss(loss_kind) ? ws.pair.nblk_bwd : ws.pair.nblk_pair;
     if (sparse) {
@@ -3399,10 +3382,8 @@ extern "C" int macr_lgcn_train_step_t(int loss_kind, int B, int d, int n_users, 
         if (int e = launch_propagate(N, d, n_layers, rowptr_t, col_t, val_t, plan_t_dev, plan_t_host, ws.dE, ws.G, ws.work, st, &spt,
                                      kSparseIn, &fuse))
             return e;
-        // w: the branch losses; w_user: bceboth only (its gradient is None elsewhere -> TF leaves it alone)
-        if (!is_pair_loss(loss_kind)) add_seg(a, w, mw, vw, ws.pair.gw, nullptr, 1, nb, kBranchSlots, 2 * d);
-        if (loss_kind == MACR_LOSS_RUBIBCEBOTH) add_seg(a, wu, mwu, vwu, ws.pair.gw + d, nullptr, 1, nb, kBranchSlots, 2 * d);
-        L.n_part2 = 0;                                  // emb_loss comes from ws.emb_acc
+        add_branch_segs(a, loss_kind, d, w, mw, vw, wu, mwu, vwu, ws.pair.gw, nb);
+        L.n_part2 = 0;                                 // emb_loss comes from ws.emb_acc
         k_lgcn_finalize<<<a.n_seg + 1, 256, 0, st>>>(a, ws.pair.scal, L, ws.emb_acc);
         MACR_CHECK_LAUNCH("lgcn_finalize", st);
         return MACR_OK;
@@ -3430,8 +3411,7 @@ extern "C" int macr_lgcn_train_step_t(int loss_kind, int B, int d, int n_users, 
         MACR_CHECK_LAUNCH("ego_branch_rows", st);
     }
     add_seg(a, T, mT, vT, ws.G, nullptr, N, nb);
-    if (!is_pair_loss(loss_kind)) add_seg(a, w, mw, vw, ws.pair.gw, nullptr, 1, nb, kBranchSlots, 2 * d);
-    if (loss_kind == MACR_LOSS_RUBIBCEBOTH) add_seg(a, wu, mwu, vwu, ws.pair.gw + d, nullptr, 1, nb, kBranchSlots, 2 * d);
+    add_branch_segs(a, loss_kind, d, w, mw, vw, wu, mwu, vwu, ws.pair.gw, nb);
     k_adam_dense<false><<<(unsigned)nb, 256, 0, st>>>(a, ws.pair.scal, L);
     MACR_CHECK_LAUNCH("adam_dense", st);
     // (dE is zero again on return, as after a step with the sparse layers: their first backward layer may read all of it)
