@@ -827,6 +827,46 @@ int macr_item_counts(int U, int K, int k, const int32_t *rankings, const int32_t
                      int n_items, const int32_t *group_of, int n_groups, int32_t *rec_cnt, int32_t *hit_cnt,
                      long long *group_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Scores and full-catalogue positions of given (query, item) pairs (additive, abi 16).  The reference's test()
+ * (macr_mf/train.py:224-251) materialises the whole (U, N) score matrix and ranklist_by_sorted keeps its first K columns;
+ * these two calls answer for ANY pair -- a held-out item at position 900 as well as one at position 3 -- what that
+ * matrix holds and where a full sort of the row would put the item, without the matrix and without the sort.
+ *   users_tab, user_ids, items, sig_u[U], sig_i[n_local], c / c_dev, d, score_kind: as in macr_score_matrix
+ *   pair_ptr  (dev) int32[U+1], pair_item (dev) int32[n_pairs]: the pairs as a CSR over the queries, item ids ascending
+ *             within a query -- the layout of the ground-truth CSR of macr_metrics_mf, which can be passed as it is;
+ *             pair_ptr[U] = n_pairs <= 2^31 - 1
+ *   mask_ptr / mask_idx (dev, both NULL: no mask): the train-mask CSR of macr_score_topk, ascending per query
+ * macr_score_pairs: out_scores[p] (dev, fp32[n_pairs]) <- the score of pair p, bit for bit what macr_score_matrix stores at
+ *   [q, item] (one arithmetic: the k-ascending fmaf chain and the score epilogue); NaN for an item outside [0, n_local).
+ * macr_rank_positions: out_pos[p] (dev, int32[n_pairs]) <- the number of candidates of query q that the project's order
+ *   (score descending, ties by ascending id) places before the pair's item: the items i in [0, n_local), not masked for q,
+ *   with (s_qi, i) before (s_qg, g).  0-based: the index the item has in macr_score_topk's ranking when K is large enough.
+ *   -1 when the pair's item is masked for q, lies outside [0, n_local) or scores NaN; a NaN-scoring candidate is before
+ *   nothing.  Exact integers, identical from run to run.  No item sharding: positions are those within [0, n_local).
+ *   workspace (dev) >= macr_rank_positions_workspace_bytes(U, n_pairs, n_local, d) bytes (0: unsupported d or bad sizes),
+ *   16-byte aligned; neither it nor out_pos need be initialised.  Four launches, no host synchronisation: the pairs' keys,
+ *   the cut of the pair lists into columns of 16, the counting pass over all U x n_local scores (the fp32 MFMA tile of the
+ *   listing pass; per score one compare with each of the column's keys instead of the threshold test), and per query the
+ *   subtraction of its masked items that rank before the pair.
+ * Refused before any device work: a score_kind outside the MACR_SCORE_* kinds, U < 1, n_local < 1, n_pairs < 0 or
+ * > 2^31 - 1, a null table / pair / output pointer, a missing sig_i / sig_u for a kind that reads it, mask_ptr without
+ * mask_idx, a null or misaligned workspace -> MACR_E_INVALID; d outside {32,64,128,256} -> MACR_E_UNSUPPORTED; a workspace
+ * too small -> MACR_E_WORKSPACE.
+ * -------------------------------------------------------------------------*/
+size_t macr_rank_positions_workspace_bytes(int U, long long n_pairs, int n_local, int d);
+int macr_score_pairs(int score_kind, int U, int n_local, int d,
+                     const float *users_tab, const int32_t *user_ids, const float *items,
+                     const float *sig_u, const float *sig_i, float c, const float *c_dev,
+                     const int32_t *pair_ptr, const int32_t *pair_item, long long n_pairs,
+                     float *out_scores, void *stream);
+int macr_rank_positions(int score_kind, int U, int n_local, int d,
+                        const float *users_tab, const int32_t *user_ids, const float *items,
+                        const float *sig_u, const float *sig_i, float c, const float *c_dev,
+                        const int32_t *mask_ptr, const int32_t *mask_idx,
+                        const int32_t *pair_ptr, const int32_t *pair_item, long long n_pairs,
+                        int32_t *out_pos, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Column means of a (rows, cols) matrix in float64 (deterministic tree):
  * the "/ n_test_users" accumulation of macr_mf/train.py:286-290 and the
  * np.mean(all_result, axis=0) of batch_test.py:151.  in_is_f32 selects input

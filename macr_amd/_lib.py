@@ -118,6 +118,9 @@ SIGNATURES = {
     "macr_metrics_mf_mean": (_i, [_i, _i, _p, _p, _p, _p, ctypes.POINTER(ctypes.c_int32), _i, _p, _p, _p, _z, _p]),
     "macr_item_counts_workspace_bytes": (_z, [_i, _i, _i]),
     "macr_item_counts": (_i, [_i, _i, _i, _p, _p, _p, _i, _p, _i, _p, _p, _p, _p, _z, _p]),
+    "macr_rank_positions_workspace_bytes": (_z, [_i, _ll, _i, _i]),
+    "macr_score_pairs": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _ll, _p, _p]),
+    "macr_rank_positions": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _ll, _p, _p, _z, _p]),
     "macr_colmean": (_i, [_p, _i, _i, _i, _p, _p]),
 }
 

@@ -214,6 +214,23 @@ __device__ __forceinline__ float orderable_f32(uint32_t u) {
 __device__ __forceinline__ uint64_t make_key(float score, int32_t id) {
     return (static_cast<uint64_t>(f32_orderable(score)) << 32) | (0xffffffffu - static_cast<uint32_t>(id));
 }
+// exact fp32 score of (query q, local item it): the k-ascending fmaf chain and the epilogue of every ranking kernel, which
+// is also what the fp32 MFMA tile accumulates (eval_kernels.hip::exact_key, rank_kernels.hip::k_score_pairs)
+template <int D, int KIND>
+__device__ __forceinline__ float exact_score(int q, int it, const float *__restrict__ users_tab, const int32_t *__restrict__ user_ids,
+                                             const float *__restrict__ items, const float *__restrict__ sig_u,
+                                             const float *__restrict__ sig_i, float c) {
+    const float *ur = users_tab + (size_t)(user_ids ? user_ids[q] : q) * D, *ir = items + (size_t)it * D;
+    float acc = 0.f;
+#pragma unroll 8
+    for (int k4 = 0; k4 < D / 4; ++k4) {
+        const float4 a = ld4(ur + 4 * k4), b = ld4(ir + 4 * k4);
+        acc = fmaf(a.x, b.x, acc); acc = fmaf(a.y, b.y, acc); acc = fmaf(a.z, b.z, acc); acc = fmaf(a.w, b.w, acc);
+    }
+    float v = acc;
+    if (score_uses_sig_i(KIND)) v = score_epilogue<KIND>(v, c, sig_i[it], score_uses_sig_u(KIND) ? sig_u[q] : 1.0f);
+    return v;
+}
 __device__ __forceinline__ float key_score(uint64_t k) { return orderable_f32(static_cast<uint32_t>(k >> 32)); }
 __device__ __forceinline__ int32_t key_id(uint64_t k) { return static_cast<int32_t>(0xffffffffu - static_cast<uint32_t>(k)); }
 

@@ -3139,16 +3139,7 @@ template <int D, int KIND>
 __device__ __forceinline__ uint64_t exact_key(int q, int id, const float *__restrict__ users_tab, const int32_t *__restrict__ user_ids,
                                               const float *__restrict__ items, const float *__restrict__ sig_u,
                                               const float *__restrict__ sig_i, float c, int item_offset) {
-    const int it = id - item_offset;
-    const float *ur = users_tab + (size_t)(user_ids ? user_ids[q] : q) * D, *ir = items + (size_t)it * D;
-    float acc = 0.f;
-#pragma unroll 8
-    for (int k4 = 0; k4 < D / 4; ++k4) {
-        const float4 a = ld4(ur + 4 * k4), b = ld4(ir + 4 * k4);
-        acc = fmaf(a.x, b.x, acc); acc = fmaf(a.y, b.y, acc); acc = fmaf(a.z, b.z, acc); acc = fmaf(a.w, b.w, acc);
-    }
-    float v = acc;
-    if (score_uses_sig_i(KIND)) v = score_epilogue<KIND>(v, c, sig_i[it], score_uses_sig_u(KIND) ? sig_u[q] : 1.0f);
+    const float v = exact_score<D, KIND>(q, id - item_offset, users_tab, user_ids, items, sig_u, sig_i, c);     // (common.hpp)
     return v == v ? make_key(v, id) : 0ull;                   // (a NaN score is no candidate: the fp32 listing test fails on it too)
 }
 

@@ -92,6 +92,7 @@ class Evaluator(object):
         self._stats_evt = None
         self._last_seeded = False
         self.gt = ops.CSR.from_lists(gt_lists, device)
+        self.n_gt = sum(len(row) for row in gt_lists)            # (gt.idx holds one padding element when this is 0)
         # (lo, hi): the `items_tab` the methods below receive is ALREADY this rank's shard, rows [lo, hi) of a catalogue
         # whose full table exists nowhere (row-sharded training, BASELINE configs[4]); None: a replicated full table
         self.local_items_range = None
@@ -281,6 +282,44 @@ class Evaluator(object):
                 n_groups = int(group_of.max()) + 1
             group_of = group_of.to(self.device).contiguous()
         return ops.item_counts(idx, self.gt, k, self.n_items, group_of, n_groups or 0)
+
+    # ------------------------------------------------------------------ full-catalogue positions (MACR_RANK_REPORT=1)
+    def rank_positions(self, kind, users_tab, user_ids, items_tab, w=None, wu=None, c=0.0, branch=None):
+        """int32[n_gt] on the device, in the order of the ground-truth CSR: for every held-out (query, item) pair the number
+        of the query's candidates -- the catalogue minus its train items -- ranked before the item by the score an
+        evaluation with the same arguments ranks by (score descending, ties by ascending id): the index rank() would
+        give the item with K large enough, wherever it stands.  -1: the item is also a train item of the query, or scores
+        NaN.  The branch factors are computed as rank() computes them (branch: the ego item rows of LightGCN's rubi2).
+        One item shard only: the counts of several shards would have to be added (NotImplementedError)."""
+        if sharding.world()[1] > 1 or self._local_own is not None or self.local_items_range is not None:
+            raise NotImplementedError("Evaluator.rank_positions ranks a whole, replicated item table: item-sharded "
+                                      "evaluation (several ranks, set_local_items) has no position count yet")
+        if items_tab.shape[0] != self.n_items:
+            raise _lib.MacrError(_lib.E_INVALID, "rank_positions: %d item rows for an evaluator of %d items" % (items_tab.shape[0], self.n_items))
+        sig_u = sig_i = None
+        both = kind in (ops.SCORE_RUBI_BOTH, ops.SCORE_DIRECT_MINUS_BOTH)
+        branch_tab = items_tab if branch is None else branch
+        if both and branch_tab.shape[1] == users_tab.shape[1]:
+            sig_i, sig_u = ops.branch_sigmoid2(branch_tab, w, None, users_tab, wu, user_ids)
+        elif kind != ops.SCORE_NORMAL:
+            sig_i = ops.branch_sigmoid(branch_tab, w)
+            if both:
+                sig_u = ops.branch_sigmoid(users_tab, wu, user_ids)
+        return ops.rank_positions(kind, users_tab, user_ids, items_tab, self.gt, sig_u, sig_i, c, self.mask, n_pairs=self.n_gt)
+
+    def rank_report(self, kind, users_tab, user_ids, items_tab, w=None, wu=None, c=0.0, branch=None, group_of=None, n_groups=None):
+        """rank_report.summarize of rank_positions: {'users', 'pairs', 'skipped', 'auc', 'mrr', 'mpr'} and, with group_of
+        (n_items group ids), 'group_pairs' / 'group_mpr' -- AUC, reciprocal rank and rank percentile of the held-out
+        items over the whole catalogue, not the first K.  One device-to-host copy (the positions)."""
+        from . import rank_report
+        pos = self.rank_positions(kind, users_tab, user_ids, items_tab, w, wu, c, branch).cpu().numpy()
+        if getattr(self, "_gt_host", None) is None:
+            mask_len = np.array([len(set(row)) for row in self._mask_lists], dtype=np.int64)
+            self._gt_host = (self.gt.ptr.cpu().numpy(), self.gt.idx[:self.n_gt].cpu().numpy(), self.n_items - mask_len)
+        gt_ptr, gt_idx, n_cand = self._gt_host
+        if group_of is not None:
+            group_of = np.asarray(group_of.cpu() if torch.is_tensor(group_of) else group_of)
+        return rank_report.summarize(pos, gt_ptr, gt_idx, n_cand, group_of, n_groups)
 
     # ------------------------------------------------------------------ MF flavour
     def test_mf(self, kind, users_tab, user_ids, items_tab, Ks, w=None, wu=None, c=0.0, branch=None):

@@ -183,6 +183,15 @@ class LightGCN(object):
             sig_u = ops.branch_sigmoid(ua, self.w_user, uid)
         return ops.score_matrix(kind, ua, uid, ia, sig_u, sig_i, self.rubi_c)
 
+    def predict(self, kind, users, items):
+        """fp32 device tensor: the score of (users[k], items[k]) for every k on the propagated tables at the model's
+        current c -- the entries of ratings(kind, users)[k, items[k]], bit for bit, without the matrix (macr_score_pairs).
+        kind: a score kind, or RUBI_EGO as in ratings()."""
+        kind, ego = (kind[0], True) if kind == self.RUBI_EGO else (kind, False)
+        ua, ia = self.propagated()
+        return ops.predict_pairs(kind, ua, users, ia.contiguous(), items, self.w, self.w_user, self.rubi_c,
+                                 branch=self.ego_items() if ego else None)
+
     def state_dict(self):
         sd = {"T": self.T, "w": self.w, "w_user": self.w_user, "rubi_c": self.rubi_c}
         for kind, st in self._opt.items():

@@ -206,6 +206,12 @@ class BPRMF(object):
             sig_u = ops.branch_sigmoid(self.user_embedding, self.w_user, uid)
         return ops.score_matrix(kind, self.user_embedding, uid, self.item_embedding, sig_u, sig_i, self.rubi_c)
 
+    def predict(self, kind, users, items):
+        """fp32 device tensor: the score of (users[k], items[k]) for every k at the model's current c -- the entries of
+        ratings(kind, users)[k, items[k]], bit for bit, without the matrix (macr_score_pairs)."""
+        self.sync()
+        return ops.predict_pairs(kind, self.user_embedding, users, self.item_embedding, items, self.w, self.w_user, self.rubi_c)
+
     def parameters(self):
         self.sync()
         return [self.user_embedding, self.item_embedding, self.w, self.w_user]

@@ -522,6 +522,78 @@ def item_counts(rankings, gt, k, n_items, group_of=None, n_groups=0):
     return rec, hit, sums
 
 
+def score_pairs(kind, users_tab, user_ids, items, pairs, sig_u=None, sig_i=None, c=0.0, n_pairs=None):
+    """fp32[n_pairs]: the score of every (query, item) pair of the CSR `pairs` over the queries (macr_score_pairs) -- bit for
+    bit what score_matrix holds at [q, item]; NaN for an item outside the table.  n_pairs: pairs.ptr[-1] where the caller
+    knows it (None: the length of pairs.idx; CSR.from_lists pads an EMPTY index array to one element)."""
+    U = users_tab.shape[0] if user_ids is None else user_ids.numel()
+    n_local, d = items.shape
+    if pairs.ptr.numel() != U + 1:
+        raise MacrError(_lib.E_INVALID, "score_pairs: the pair CSR has %d rows for %d queries" % (pairs.ptr.numel() - 1, U))
+    n_pairs = pairs.idx.numel() if n_pairs is None else int(n_pairs)
+    out = torch.empty(n_pairs, dtype=_f32, device=items.device)
+    cv, cp = _c_args(c)
+    check(_lib.lib().macr_score_pairs(kind, U, n_local, d, _ptr(users_tab, _f32), _ptr(user_ids, _i32, True), _ptr(items, _f32),
+                                      _ptr(sig_u, _f32, True), _ptr(sig_i, _f32, True), cv, cp, _ptr(pairs.ptr, _i32),
+                                      _ptr(pairs.idx, _i32), n_pairs, _ptr(out), _stream()))
+    return out
+
+
+def predict_pairs(kind, users_tab, users, items_tab, items, w=None, wu=None, c=0.0, branch=None):
+    """fp32[n]: the score of (users[k], items[k]) for every k -- the `predict` of the models.  Every pair is a query of its
+    own with one item, so users may repeat; the branch factors sigmoid(row . w) are the ones an evaluation computes (branch:
+    the table the items' factors come from, None: items_tab)."""
+    dev = items_tab.device
+    uid = torch.as_tensor(users, dtype=_i32, device=dev).reshape(-1).contiguous()
+    iid = torch.as_tensor(items, dtype=_i32, device=dev).reshape(-1).contiguous()
+    if uid.numel() != iid.numel():
+        raise ValueError("predict: %d users for %d items" % (uid.numel(), iid.numel()))
+    if uid.numel() == 0:
+        return torch.empty(0, dtype=_f32, device=dev)
+    sig_u = sig_i = None
+    if kind != SCORE_NORMAL:
+        sig_i = branch_sigmoid(items_tab if branch is None else branch, w)
+    if kind in (SCORE_RUBI_BOTH, SCORE_DIRECT_MINUS_BOTH):
+        sig_u = branch_sigmoid(users_tab, wu, uid)
+    pairs = CSR(torch.arange(uid.numel() + 1, dtype=_i32, device=dev), iid)
+    return score_pairs(kind, users_tab, uid, items_tab, pairs, sig_u, sig_i, c)
+
+
+_rank_ws_cache = {}
+
+
+def _rank_workspace(need, device):
+    """Scratch of macr_rank_positions (keys, columns, counters); one buffer per device, grown on demand.  The call
+    initialises what it reads."""
+    ws = _rank_ws_cache.get(device)
+    if ws is None or ws.numel() < need:
+        ws = _rank_ws_cache[device] = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+    return ws
+
+
+def rank_positions(kind, users_tab, user_ids, items, pairs, sig_u=None, sig_i=None, c=0.0, mask=None, n_pairs=None):
+    """int32[n_pairs]: for every (query, item) pair of the CSR `pairs`, the number of the query's candidates (the items of
+    the table outside its `mask` CSR) that rank before the item -- its 0-based position in the full ranking, score
+    descending and ties by ascending id; -1 for a pair that is masked, outside the table or NaN (macr_rank_positions)."""
+    U = users_tab.shape[0] if user_ids is None else user_ids.numel()
+    n_local, d = items.shape
+    if pairs.ptr.numel() != U + 1 or (mask is not None and mask.ptr.numel() != U + 1):
+        raise MacrError(_lib.E_INVALID, "rank_positions: the pair / mask CSR does not have one row per query (%d)" % U)
+    n_pairs = pairs.idx.numel() if n_pairs is None else int(n_pairs)
+    L = _lib.lib()
+    out = torch.empty(n_pairs, dtype=_i32, device=items.device)
+    need = L.macr_rank_positions_workspace_bytes(U, n_pairs, n_local, d)
+    ws = _rank_workspace(need, items.device)
+    cv, cp = _c_args(c)
+    check(L.macr_rank_positions(kind, U, n_local, d, _ptr(users_tab, _f32), _ptr(user_ids, _i32, True), _ptr(items, _f32),
+                                _ptr(sig_u, _f32, True), _ptr(sig_i, _f32, True), cv, cp,
+                                _ptr(mask.ptr, _i32) if mask is not None else None,
+                                _ptr(mask.idx, _i32) if mask is not None else None,
+                                _ptr(pairs.ptr, _i32), _ptr(pairs.idx, _i32), n_pairs, _ptr(out), _ptr(ws),
+                                ws.numel(), _stream()))
+    return out
+
+
 def colmean(x, out=None):
     """out: optional float64 device or pinned host tensor of x.shape[1:]"""
     rows = x.shape[0]

@@ -29,9 +29,10 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from utility.helper import early_stopping, ensureDir          # noqa: E402
 from utility.batch_test import *                              # noqa: E402,F401,F403  (args, data_generator, test ...)
-from utility.branch_ranking import test, test_sweep, item_diagnostic           # noqa: E402,F811  (+ --test rubi1 / rubi2)
+from utility.branch_ranking import test, test_sweep, item_diagnostic, rank_diagnostic           # noqa: E402,F811  (+ --test rubi1 / rubi2)
 from macr_amd.lightgcn import LightGCN as _LightGCN           # noqa: E402
 from macr_amd.mf import Session                               # noqa: E402
+from macr_amd import rank_report                               # noqa: E402
 
 logging.getLogger().setLevel(logging.INFO)
 
@@ -125,6 +126,9 @@ def main(sweep=False):
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not torch.distributed.is_initialized():
         torch.distributed.init_process_group(os.environ.get("MACR_DIST_BACKEND", "nccl"))
     main_rank = sharding.is_main()           # several ranks: replicas train, ONE prints / logs / writes (rank 0)
+    if rank_report.enabled() and sharding.world()[1] > 1:
+        raise SystemExit("MACR_RANK_REPORT=1 counts positions over a whole, replicated item table: it has no item-sharded "
+                         "form; unset MACR_RANK_REPORT or evaluate on one rank")
 
     def say(text, end='\n'):
         if main_rank:
@@ -249,9 +253,12 @@ def main(sweep=False):
                         c, ret['recall'][0], ret['recall'][-1], ret['hr'][0], ret['hr'][-1], ret['ndcg'][0],
                         ret['ndcg'][-1])
             ret['hr'][0] = best_hr
-            if sweep and args.out == 1:                  # the diagnostic of the chosen c only (no hit at any c: the last one)
+            if sweep and (args.out == 1 or rank_report.enabled()):    # the diagnostics of the chosen c only (no hit at any c: the last one)
                 model.update_c(sess, c_values[-1] if best_c is None else best_c)
-                item_diagnostic(sess, model, users_to_test, args.test)
+                if args.out == 1:
+                    item_diagnostic(sess, model, users_to_test, args.test)
+                if rank_report.enabled():
+                    rank_diagnostic(sess, model, users_to_test, args.test)
                 model.update_c(sess, c_values[-1])       # (what the loop left, and what a checkpoint records)
             if best_hr > best_c_hr:                      # config['best_c_epoch'] of the reference (:880)
                 best_c_hr, best_c_epoch = best_hr, epoch

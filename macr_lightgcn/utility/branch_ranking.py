@@ -10,7 +10,7 @@ import torch
 
 from utility import batch_test as _bt
 
-from macr_amd import ops, popularity, sharding
+from macr_amd import ops, popularity, rank_report, sharding
 from macr_amd.eval_cache import EvaluatorCache
 from macr_amd.evaluator import Evaluator
 
@@ -48,7 +48,38 @@ def test(sess, model, users_to_test, drop_flag=False, train_set_flag=0, method="
         ret = {k: np.asarray(v) for k, v in ret.items()}
     if _bt.args.out == 1:
         item_diagnostic(sess, model, users_to_test, method)
+    if rank_report.enabled():
+        rank_diagnostic(sess, model, users_to_test, method)
     return ret
+
+
+def _popularity_tables():
+    """{'group_of': the popularity group of every item, 'n_test': its test interactions}, built once"""
+    if not _popularity:
+        data = _bt.data_generator
+        counts = np.zeros(_bt.ITEM_NUM, dtype=np.int64)
+        for items in data.train_items.values():
+            np.add.at(counts, np.asarray(items, dtype=np.int64), 1)
+        n_test = np.zeros(_bt.ITEM_NUM, dtype=np.int64)
+        for item, users in data.test_item_set.items():
+            n_test[item] = len(users)
+        _popularity.update(group_of=popularity.item_groups(counts), n_test=n_test)
+    return _popularity
+
+
+def rank_diagnostic(sess, model, users_to_test, method):
+    """MACR_RANK_REPORT=1: one line on where the held-out items stand in the FULL ranking test() scores with the same arguments
+    (same score kind, the model's current c -- after a sweep the chosen one): AUC, reciprocal rank and rank percentile over
+    the whole catalogue, overall and per train-popularity group of --out 1 (macr_amd/rank_report.py).  The main rank prints."""
+    one_branch = method in _ITEM_BRANCH
+    evaluator, uid = (_evaluator_for if one_branch else _bt._evaluator_for)(model, users_to_test)
+    kind = ops.SCORE_RUBI if one_branch else _bt._METHODS[method]
+    ua, ia = model.propagated()
+    rep = evaluator.rank_report(kind, ua, uid, ia.contiguous(), model.w, model.w_user, model.rubi_c,
+                                branch=_branch(model, method) if one_branch else None,
+                                group_of=_popularity_tables()["group_of"], n_groups=len(popularity.POINTS) + 1)
+    if sharding.is_main():
+        print(rank_report.format_line(rep))
 
 
 def item_diagnostic(sess, model, users_to_test, method):
@@ -59,15 +90,7 @@ def item_diagnostic(sess, model, users_to_test, method):
     one_branch = method in _ITEM_BRANCH
     evaluator, uid = (_evaluator_for if one_branch else _bt._evaluator_for)(model, users_to_test)
     kind = ops.SCORE_RUBI if one_branch else _bt._METHODS[method]
-    data = _bt.data_generator
-    if not _popularity:
-        counts = np.zeros(_bt.ITEM_NUM, dtype=np.int64)
-        for items in data.train_items.values():
-            np.add.at(counts, np.asarray(items, dtype=np.int64), 1)
-        n_test = np.zeros(_bt.ITEM_NUM, dtype=np.int64)
-        for item, users in data.test_item_set.items():
-            n_test[item] = len(users)
-        _popularity.update(group_of=popularity.item_groups(counts), n_test=n_test)
+    _popularity_tables()
     ua, ia = model.propagated()
     rec, hit, sums = evaluator.item_accuracy(kind, ua, uid, ia.contiguous(), ITEM_ACC_K, model.w, model.w_user, model.rubi_c,
                                              branch=_branch(model, method) if one_branch else None,

@@ -24,7 +24,7 @@ import torch
 from batch_test import *          # noqa: F401,F403  (args, data, Ks, BATCH_SIZE, ITEM_NUM, USER_NUM)
 from model import BPRMF, Session
 
-from macr_amd import ops, popularity
+from macr_amd import ops, popularity, rank_report
 from macr_amd.evaluator import Evaluator
 from macr_amd.eval_cache import EvaluatorCache
 from macr_amd.metrics_host import (precision_at_k, dcg_at_k, ndcg_at_k, recall_at_k, hit_at_k,   # noqa: F401
@@ -70,6 +70,8 @@ def test(sess, model, test_users, batch_test_flag=False, model_type='o', valid_s
                                 model.w, model.w_user, model.rubi_c)
     if args.out == 1:
         item_diagnostic(sess, model, test_users, model_type, valid_set)
+    if rank_report.enabled():
+        rank_diagnostic(sess, model, test_users, model_type, valid_set)
     return ret
 
 
@@ -102,6 +104,21 @@ def item_diagnostic(sess, model, test_users, model_type='o', valid_set="test"):
                                              model.w, model.w_user, model.rubi_c, group_of=group_of, n_groups=len(rate))
     if sharding.is_main():
         popularity.emit(rec, hit, sums, n_test, group_of, ITEM_ACC_K, ITEM_ACC_FILE)
+
+
+def rank_diagnostic(sess, model, test_users, model_type='o', valid_set="test"):
+    """MACR_RANK_REPORT=1: one line on where the held-out items stand in the FULL ranking test() scores with the same arguments
+    (same score kind, the model's current c) -- AUC, reciprocal rank and rank percentile over the whole catalogue, overall
+    and per train-popularity group of --out 1 (macr_amd/rank_report.py).  The main rank prints."""
+    from macr_amd import sharding
+    evaluator, uid = _evaluator_for(model, test_users, valid_set)
+    model.sync()
+    if "groups" not in _n_test:
+        _n_test["groups"] = _item_groups()
+    rep = evaluator.rank_report(_MODEL_TYPES[model_type], model.user_embedding, uid, model.item_embedding, model.w, model.w_user,
+                                model.rubi_c, group_of=_n_test["groups"], n_groups=len(rate))
+    if sharding.is_main():
+        print(rank_report.format_line(rep))
 
 
 def test_sweep(sess, model, test_users, cs, model_type='rubi_both', valid_set="test"):
@@ -187,6 +204,9 @@ def main(sweep=False):
         # item-sharded evaluation across the node's GPUs (MACR_DIST_BACKEND=gloo: test rig, several ranks on one GPU)
         torch.distributed.init_process_group(os.environ.get("MACR_DIST_BACKEND", "nccl"))
     main_rank = sharding.is_main()           # several ranks: replicas train, ONE prints / logs / writes (rank 0)
+    if rank_report.enabled() and (args.row_shard == 1 or sharding.world()[1] > 1):
+        raise SystemExit("MACR_RANK_REPORT=1 counts positions over a whole, replicated item table: it has no %s form; "
+                         "unset MACR_RANK_REPORT or evaluate on one rank" % ("--row_shard 1" if args.row_shard == 1 else "item-sharded"))
 
     def say(text):
         if main_rank:
@@ -309,9 +329,12 @@ def main(sweep=False):
                 if ret['hit_ratio'][0] > best[0]:
                     best = (ret['hit_ratio'][0], ret['recall'][0], ret['precision'][0], ret['ndcg'][0], c)
             ret['hit_ratio'][0], ret['recall'][0], ret['precision'][0], ret['ndcg'][0] = best[:4]
-            if sweep and args.out == 1:              # the diagnostic of the chosen c only (no hit at any c: the last one)
+            if sweep and (args.out == 1 or rank_report.enabled()):       # the diagnostics of the chosen c only (no hit at any c: the last one)
                 model.update_c(sess, best[4] if best[0] > 0 else c_values[-1])
-                item_diagnostic(sess, model, users_to_test, rubi_type, args.valid_set)
+                if args.out == 1:
+                    item_diagnostic(sess, model, users_to_test, rubi_type, args.valid_set)
+                if rank_report.enabled():
+                    rank_diagnostic(sess, model, users_to_test, rubi_type, args.valid_set)
                 model.update_c(sess, c_values[-1])   # (what the loop left, and what a checkpoint records)
             if best[0] > config['best_c_hr']:
                 config['best_c_hr'], config['best_c'], config['best_c_epoch'] = best[0], best[4], epoch
