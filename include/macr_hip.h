@@ -164,7 +164,8 @@ typedef struct macr_hyper {
  *     call that deferred.  macr_mf_train_flush takes no flag: the pass it completes is per-row;
  *   - workspace >= macr_mf_train_workspace_bytes_det(B, d) (>= macr_mf_train_workspace_bytes(B, d); 0 for an unsupported
  *     d), else MACR_E_WORKSPACE;
- *   - macr_mf_train_step_lazy refuses it with MACR_E_UNSUPPORTED; the macr_shard_* entry points do not know it.
+ *   - macr_mf_train_step_lazy refuses it with MACR_E_UNSUPPORTED; the macr_shard_* entry points do not know it (the row-sharded
+ *     step has a mode of its own, with its own contract: macr_shard_*_det below).
  * How: every gradient row is staged with plain stores and summed by ONE owner in the order of the (stable) reference sort, at
  * every B; a row with more references than one chunk is a two-level sum of fixed shape (chunk sums to slots of their own,
  * then the owner adds the slots in position order); the branch-vector gradient is one partial row per backward block,
@@ -355,6 +356,47 @@ int macr_shard_apply_lazy(int loss_kind, int B, int d, int n_users_loc, int n_it
                           float *mP, float *vP, float *mQ, float *vQ, float *mw, float *vw, float *mwu, float *vwu,
                           float *gP, float *gQ, int32_t *touchedP, int32_t *touchedQ, const macr_hyper *hp,
                           const macr_lazy_adam *lazy, void *workspace, size_t workspace_bytes, void *stream);
+/* ---------------------------------------------------------------------------
+ * The bit-reproducible row-sharded step (additive, abi 16; host switch MACR_SHARD_DETERMINISTIC=1, macr_amd/sharded_train.py).
+ * CONTRACT: with the _det entry points in place of their plain counterparts -- and the cross-rank sums of the split step taken
+ * through macr_shard_fold_ranks -- the losses on every rank, every rank's shard of P, Q and their Adam slots, w, wu and their
+ * slots, adam_pow and the row stamps after a flush are a function only of the batches, the library build, the device model,
+ * the number of ranks, the row layout, the step form (replicated / split) and the lazy period: two runs agree bit for bit,
+ * and nothing depends on the order in which a collective adds its operands.  NOT promised: equal bits across numbers of
+ * ranks, layouts or step forms (a long row's two-level sum takes its shape from where the run lies in the rank's sorted list),
+ * nor against macr_mf_train_step.  The results differ from the plain entry points' by fp32 rounding only.
+ *   macr_shard_workspace_bytes_det  >= macr_shard_workspace_bytes (0 where that is 0).  The plain layout is a PREFIX of this one:
+ *       macr_shard_gather(_lazy), _forward, _bxb, _forward_slice, _stage, _slice and _route run unchanged on a workspace of
+ *       either size; the three calls below refuse a smaller one with MACR_E_WORKSPACE.  Behind the prefix: the chunk sums of
+ *       the cut runs (2 * ceil(3B / min(d/4, 16)) rows of d floats) and one 2*d row per backward block.
+ *   macr_shard_backward_det, macr_shard_backward_slice_det   arguments and answers of the plain calls.  Branch kinds: every
+ *       backward block stores its branch-vector partial row, and one kernel folds the rows into the returned region in block
+ *       order (the slice form: the blocks of the slice).  Per-pair kinds: what the plain call runs (no atomics there).
+ *   macr_shard_apply_det   arguments of macr_shard_apply_lazy; lazy may be NULL (the dense pass).  Every row of the shard has
+ *       ONE owner, which sums the row's staged gradient rows in the order of the (stable) reference sort -- a run cut by a
+ *       chunk boundary as a two-level sum of fixed shape -- whatever MACR_SEG_UNFUSED says; then the dense or the lazy pass,
+ *       which have one owner per row and no atomics.  gP, gQ and the row flags are clean on return, as after the plain call.
+ *   macr_shard_fold_ranks  out[e] = parts[0][e] + parts[1][e] + .. + parts[world-1][e] (parts: (dev) fp32[world][n]), added in
+ *       rank order.  The split step sums two regions that several ranks fill at the same indices (the forward region's loss
+ *       partials, the branch-vector partial rows): each rank places its region in row `rank` of a zeroed [world][n] buffer,
+ *       the buffer is all-reduced -- every element is x + 0 + .. + 0, exact in any order -- and this call folds it.
+ * The replicated step needs no fold: rows3 and the (B,B) partials are disjoint across the ranks, the branch rows are rank 0's.
+ * -------------------------------------------------------------------------*/
+size_t macr_shard_workspace_bytes_det(int B, int d);
+int macr_shard_backward_det(int loss_kind, int B, int d, const float *rows3, const float *w, const float *wu,
+                            float *adam_pow, const macr_hyper *hp, float *losses, void **branch_grads,
+                            size_t *branch_bytes, void *workspace, size_t workspace_bytes, void *stream);
+int macr_shard_backward_slice_det(int loss_kind, int B, int d, int t0, int n, const float *rows3_slice, const float *w,
+                                  const float *wu, float *adam_pow, const macr_hyper *hp, float *losses,
+                                  float *stage_slice, void **branch_grads, size_t *branch_bytes, void *workspace,
+                                  size_t workspace_bytes, void *stream);
+int macr_shard_apply_det(int loss_kind, int B, int d, int n_users_loc, int n_items_loc, int u_lo, int u_stride, int i_lo,
+                         int i_stride, const int32_t *u, const int32_t *i, const int32_t *j,
+                         float *P_loc, float *Q_loc, float *w, float *wu,
+                         float *mP, float *vP, float *mQ, float *vQ, float *mw, float *vw, float *mwu, float *vwu,
+                         float *gP, float *gQ, int32_t *touchedP, int32_t *touchedQ, const macr_hyper *hp,
+                         const macr_lazy_adam *lazy, void *workspace, size_t workspace_bytes, void *stream);
+int macr_shard_fold_ranks(int world, long long n, const float *parts, float *out, void *stream);
 /* every row of both tables brought to the current step (n_rows_p / n_rows_q: rows of the local tables) */
 int macr_lazy_flush(int d, long long n_rows_p, long long n_rows_q, float *P, float *Q, float *mP, float *vP, float *mQ,
                     float *vQ, const macr_hyper *hp, const macr_lazy_adam *lazy, void *stream);

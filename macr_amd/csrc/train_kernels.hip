@@ -2837,12 +2837,26 @@ static ShardWs carve_shard_ws(void *base, int B, int d) {
     w.bytes = w.pair.bytes + align_up(3 * (size_t)B * 4, 256);
     return w;
 }
+// MACR_SHARD_DETERMINISTIC: the plain layout -- iota included -- is a PREFIX of this one (gather, forward, bxb, the slice forward,
+// stage and route carve the plain layout and find everything where it is), and behind it lies the scratch of the two ordered
+// sums.  (carve_pair_ws_det would append at pair.bytes, which is where iota lives here: hence a carve of its own.)
+static ShardWs carve_shard_ws_det(void *base, int B, int d) {
+    ShardWs w = carve_shard_ws(base, B, d);
+    const int ch = d / 4 < 16 ? d / 4 : 16;                 // = CH of k_seg_reduce
+    char *p = static_cast<char *>(base);
+    auto take = [&](size_t bytes) { void *r = p ? p + w.bytes : nullptr; w.bytes += align_up(bytes, 256); return r; };
+    w.pair.cpart = static_cast<float *>(take(2 * ((3 * (size_t)B + ch - 1) / ch) * d * 4));
+    w.pair.wblk = static_cast<float *>(take((size_t)w.pair.nblk_bwd * 2 * d * 4));
+    return w;
+}
 static inline int grid_for(long long n) { const long long g = (n + 255) / 256; return (int)(g < 4096 ? (g > 0 ? g : 1) : 4096); }
 
-#define MACR_SHARD_COMMON(who)                                                                                         \
+#define MACR_SHARD_COMMON(who) MACR_SHARD_COMMON_AS(who, false)
+// det (a runtime flag): the workspace of macr_shard_workspace_bytes_det
+#define MACR_SHARD_COMMON_AS(who, det)                                                                                 \
     MACR_REQUIRE(B > 0 && dim_supported(d), B > 0 ? MACR_E_UNSUPPORTED : MACR_E_INVALID, who ": B=%d d=%d", B, d);      \
     MACR_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0, MACR_E_INVALID, who ": workspace"); \
-    ShardWs sw = carve_shard_ws(workspace, B, d);                                                                      \
+    ShardWs sw = (det) ? carve_shard_ws_det(workspace, B, d) : carve_shard_ws(workspace, B, d);                        \
     MACR_REQUIRE(workspace_bytes >= sw.bytes, MACR_E_WORKSPACE, who ": workspace %zu < %zu bytes", workspace_bytes, sw.bytes); \
     const PairWs &ws = sw.pair;                                                                                        \
     hipStream_t st = as_stream(stream)
@@ -2878,6 +2892,11 @@ static int shard_gather(int B, int d, const float *P_loc, const float *mP, const
 extern "C" size_t macr_shard_workspace_bytes(int B, int d) {
     if (B <= 0 || !dim_supported(d)) return 0;
     return carve_shard_ws(nullptr, B, d).bytes;
+}
+
+extern "C" size_t macr_shard_workspace_bytes_det(int B, int d) {
+    if (B <= 0 || !dim_supported(d)) return 0;
+    return carve_shard_ws_det(nullptr, B, d).bytes;
 }
 
 extern "C" int macr_shard_gather(int B, int d, const float *P_loc, int u_lo, int u_stride, int n_users_loc, const float *Q_loc,
@@ -2949,14 +2968,16 @@ extern "C" int macr_shard_bxb(int B, int d, int rank, int world, void **partials
 
 /* gradient rows of the whole batch into the staging buffer of the workspace; losses (dev) fp32[3]; the branch-vector
  * partial rows (returned region) are replicated work: broadcast rank 0's so that w, w_user stay bit-identical */
-extern "C" int macr_shard_backward(int loss_kind, int B, int d, const float *rows3, const float *w, const float *wu,
-                                   float *adam_pow, const macr_hyper *hp, float *losses, void **branch_grads,
-                                   size_t *branch_bytes, void *workspace, size_t workspace_bytes, void *stream) {
+namespace macr {
+// det: macr_shard_backward_det -- the branch-vector gradient as one partial row per backward block (wblk), folded in block order
+static int shard_backward(bool det, int loss_kind, int B, int d, const float *rows3, const float *w, const float *wu,
+                          float *adam_pow, const macr_hyper *hp, float *losses, void **branch_grads,
+                          size_t *branch_bytes, void *workspace, size_t workspace_bytes, void *stream) {
     MACR_REQUIRE(loss_kind == MACR_LOSS_RUBIBCEBOTH || loss_kind == MACR_LOSS_RUBIBCE || loss_kind == MACR_LOSS_NORMALBCE ||
                      loss_kind == MACR_LOSS_BPR, MACR_E_INVALID, "shard_backward: loss_kind=%d", loss_kind);
     MACR_REQUIRE(rows3 && w && wu && adam_pow && losses, MACR_E_INVALID, "shard_backward: null pointer");
     if (int e = validate_hyper(hp, "shard_backward")) return e;
-    MACR_SHARD_COMMON("shard_backward");
+    MACR_SHARD_COMMON_AS("shard_backward", det);
     LossArgs L = loss_args(loss_kind, B, hp, losses);
     L.part = ws.part; L.n_part = ws.nblk_pair; L.part2 = nullptr; L.n_part2 = 0;
     L.lpart = ws.lpart; L.n_lpart = ws.nrb * ws.ncbx;
@@ -2976,14 +2997,40 @@ extern "C" int macr_shard_backward(int loss_kind, int B, int d, const float *row
         if (branch_bytes) *branch_bytes = 0;
         return MACR_OK;
     }
-    MACR_DISPATCH_LPR(d, (k_pair_bwd_stage<LPR><<<ws.nblk_bwd + 1, 256, 0, st>>>(
-                             B, ws.Bp, ws.nrb, ws.ncb, sw.iota, sw.iota + B, sw.iota + 2 * (size_t)B, rows3, Isrc, w, wu, ws.fwd,
-                             ws.rowpart, ws.colpart, ws.stage, ws.gw, hp->alpha, hp->beta, coef, adam_pow, ws.scal, hp->lr,
-                             hp->beta1, hp->beta2, L)));
-    MACR_CHECK_LAUNCH("pair_bwd", st);
+    if (det) {
+        MACR_DISPATCH_LPR(d, (k_pair_bwd_stage<LPR, false, false, true><<<ws.nblk_bwd + 1, 256, 0, st>>>(
+                                 B, ws.Bp, ws.nrb, ws.ncb, sw.iota, sw.iota + B, sw.iota + 2 * (size_t)B, rows3, Isrc, w, wu, ws.fwd,
+                                 ws.rowpart, ws.colpart, ws.stage, ws.wblk, hp->alpha, hp->beta, coef, adam_pow, ws.scal, hp->lr,
+                                 hp->beta1, hp->beta2, L)));
+        MACR_CHECK_LAUNCH("pair_bwd", st);
+        k_branch_fold<<<(kBranchSlots * 2 * d + 255) / 256, 256, 0, st>>>(ws.nblk_bwd, 2 * d, ws.wblk, ws.gw);
+        MACR_CHECK_LAUNCH("branch_fold", st);
+    } else {
+        MACR_DISPATCH_LPR(d, (k_pair_bwd_stage<LPR><<<ws.nblk_bwd + 1, 256, 0, st>>>(
+                                 B, ws.Bp, ws.nrb, ws.ncb, sw.iota, sw.iota + B, sw.iota + 2 * (size_t)B, rows3, Isrc, w, wu, ws.fwd,
+                                 ws.rowpart, ws.colpart, ws.stage, ws.gw, hp->alpha, hp->beta, coef, adam_pow, ws.scal, hp->lr,
+                                 hp->beta1, hp->beta2, L)));
+        MACR_CHECK_LAUNCH("pair_bwd", st);
+    }
     if (branch_grads) *branch_grads = ws.gw;
     if (branch_bytes) *branch_bytes = (size_t)kBranchSlots * 2 * d * 4;
     return MACR_OK;
+}
+}  // namespace macr
+
+extern "C" int macr_shard_backward(int loss_kind, int B, int d, const float *rows3, const float *w, const float *wu,
+                                   float *adam_pow, const macr_hyper *hp, float *losses, void **branch_grads,
+                                   size_t *branch_bytes, void *workspace, size_t workspace_bytes, void *stream) {
+    return shard_backward(false, loss_kind, B, d, rows3, w, wu, adam_pow, hp, losses, branch_grads, branch_bytes, workspace,
+                          workspace_bytes, stream);
+}
+
+/* macr_shard_backward of the bit-reproducible sharded step (MACR_SHARD_DETERMINISTIC, include/macr_hip.h) */
+extern "C" int macr_shard_backward_det(int loss_kind, int B, int d, const float *rows3, const float *w, const float *wu,
+                                       float *adam_pow, const macr_hyper *hp, float *losses, void **branch_grads,
+                                       size_t *branch_bytes, void *workspace, size_t workspace_bytes, void *stream) {
+    return shard_backward(true, loss_kind, B, d, rows3, w, wu, adam_pow, hp, losses, branch_grads, branch_bytes, workspace,
+                          workspace_bytes, stream);
 }
 
 /* ---- the SPLIT step (round 5): forward and backward of a rank's SLICE of the batch only ------------------------------------
@@ -3057,16 +3104,17 @@ extern "C" int macr_shard_forward_slice(int loss_kind, int B, int d, int t0, int
 /* backward of the slice (after the partial sums of macr_shard_bxb have been summed over the ranks): gradient rows of positions
  * t0 .. t0+n-1 into stage_slice (dev) fp32[3][n][d]; losses of the WHOLE batch (identical on every rank); the branch-vector
  * partial rows (returned region) hold this slice's share: sum them over the ranks. */
-extern "C" int macr_shard_backward_slice(int loss_kind, int B, int d, int t0, int n, const float *rows3_slice, const float *w,
-                                         const float *wu, float *adam_pow, const macr_hyper *hp, float *losses,
-                                         float *stage_slice, void **branch_grads, size_t *branch_bytes, void *workspace,
-                                         size_t workspace_bytes, void *stream) {
+namespace macr {
+static int shard_backward_slice(bool det, int loss_kind, int B, int d, int t0, int n, const float *rows3_slice, const float *w,
+                                const float *wu, float *adam_pow, const macr_hyper *hp, float *losses,
+                                float *stage_slice, void **branch_grads, size_t *branch_bytes, void *workspace,
+                                size_t workspace_bytes, void *stream) {
     MACR_REQUIRE(loss_kind == MACR_LOSS_RUBIBCEBOTH || loss_kind == MACR_LOSS_RUBIBCE, MACR_E_UNSUPPORTED,
                  "shard_backward_slice: loss_kind=%d", loss_kind);
     MACR_REQUIRE(w && wu && adam_pow && losses && t0 >= 0 && n >= 0 && t0 + n <= B && (n == 0 || (rows3_slice && stage_slice)),
                  MACR_E_INVALID, "shard_backward_slice: bad argument");
     if (int e = validate_hyper(hp, "shard_backward_slice")) return e;
-    MACR_SHARD_COMMON("shard_backward_slice");
+    MACR_SHARD_COMMON_AS("shard_backward_slice", det);
     LossArgs L = loss_args(loss_kind, B, hp, losses);
     L.part = ws.part; L.n_part = ws.nblk_pair; L.part2 = nullptr; L.n_part2 = 0;      // (every rank's blocks were summed index by index)
     L.lpart = ws.lpart; L.n_lpart = ws.nrb * ws.ncbx;
@@ -3076,13 +3124,66 @@ extern "C" int macr_shard_backward_slice(int loss_kind, int B, int d, int t0, in
     nblk = nblk < 4096 ? nblk : 4096;
     // (the branch-vector partial rows were zeroed by the forward of the slice; a slice without triples still runs the last block:
     // the step's lr_t, the beta powers and the losses)
-    MACR_DISPATCH_LPR(d, (k_pair_bwd_stage<LPR><<<nblk + 1, 256, 0, st>>>(
-                             n, ws.Bp, ws.nrb, ws.ncb, sw.iota, sw.iota + n, sw.iota + 2 * (size_t)n, rows3_slice,
-                             rows3_slice + (size_t)n * d, w, wu, ws.fwd + t0, ws.rowpart + t0, ws.colpart + t0, stage_slice, ws.gw,
-                             hp->alpha, hp->beta, coef, adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, L, nullptr, B)));
-    MACR_CHECK_LAUNCH("pair_bwd", st);
+    if (det) {
+        // one partial row per block of the SLICE (nblk <= ws.nblk_bwd rows of wblk), folded in block order into this rank's
+        // share of gw: a function of the slice alone (an empty slice folds nothing: zeros)
+        MACR_DISPATCH_LPR(d, (k_pair_bwd_stage<LPR, false, false, true><<<nblk + 1, 256, 0, st>>>(
+                                 n, ws.Bp, ws.nrb, ws.ncb, sw.iota, sw.iota + n, sw.iota + 2 * (size_t)n, rows3_slice,
+                                 rows3_slice + (size_t)n * d, w, wu, ws.fwd + t0, ws.rowpart + t0, ws.colpart + t0, stage_slice, ws.wblk,
+                                 hp->alpha, hp->beta, coef, adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, L, nullptr, B)));
+        MACR_CHECK_LAUNCH("pair_bwd", st);
+        k_branch_fold<<<(kBranchSlots * 2 * d + 255) / 256, 256, 0, st>>>(nblk, 2 * d, ws.wblk, ws.gw);
+        MACR_CHECK_LAUNCH("branch_fold", st);
+    } else {
+        MACR_DISPATCH_LPR(d, (k_pair_bwd_stage<LPR><<<nblk + 1, 256, 0, st>>>(
+                                 n, ws.Bp, ws.nrb, ws.ncb, sw.iota, sw.iota + n, sw.iota + 2 * (size_t)n, rows3_slice,
+                                 rows3_slice + (size_t)n * d, w, wu, ws.fwd + t0, ws.rowpart + t0, ws.colpart + t0, stage_slice, ws.gw,
+                                 hp->alpha, hp->beta, coef, adam_pow, ws.scal, hp->lr, hp->beta1, hp->beta2, L, nullptr, B)));
+        MACR_CHECK_LAUNCH("pair_bwd", st);
+    }
     if (branch_grads) *branch_grads = ws.gw;
     if (branch_bytes) *branch_bytes = (size_t)kBranchSlots * 2 * d * 4;
+    return MACR_OK;
+}
+
+// out[e] = parts[0][e] + parts[1][e] + .. + parts[world - 1][e], added in rank order by one thread per element
+__global__ __launch_bounds__(256) void k_fold_ranks(int world, long long n, const float *__restrict__ parts, float *__restrict__ out) {
+    for (long long e = blockIdx.x * 256LL + threadIdx.x; e < n; e += gridDim.x * 256LL) {
+        float acc = parts[e];
+        for (int r = 1; r < world; ++r) acc += parts[(size_t)r * n + e];
+        out[e] = acc;
+    }
+}
+}  // namespace macr
+
+extern "C" int macr_shard_backward_slice(int loss_kind, int B, int d, int t0, int n, const float *rows3_slice, const float *w,
+                                         const float *wu, float *adam_pow, const macr_hyper *hp, float *losses,
+                                         float *stage_slice, void **branch_grads, size_t *branch_bytes, void *workspace,
+                                         size_t workspace_bytes, void *stream) {
+    return shard_backward_slice(false, loss_kind, B, d, t0, n, rows3_slice, w, wu, adam_pow, hp, losses, stage_slice, branch_grads,
+                                branch_bytes, workspace, workspace_bytes, stream);
+}
+
+/* macr_shard_backward_slice of the bit-reproducible sharded step */
+extern "C" int macr_shard_backward_slice_det(int loss_kind, int B, int d, int t0, int n, const float *rows3_slice, const float *w,
+                                             const float *wu, float *adam_pow, const macr_hyper *hp, float *losses,
+                                             float *stage_slice, void **branch_grads, size_t *branch_bytes, void *workspace,
+                                             size_t workspace_bytes, void *stream) {
+    return shard_backward_slice(true, loss_kind, B, d, t0, n, rows3_slice, w, wu, adam_pow, hp, losses, stage_slice, branch_grads,
+                                branch_bytes, workspace, workspace_bytes, stream);
+}
+
+/* The cross-rank sums of the bit-reproducible split step.  A sum-all-reduce whose operands are zero wherever another rank's is
+ * not computes x + 0 + .. + 0: exact in whatever order the collective adds.  So a region that several ranks fill at the SAME
+ * indices (the loss partials of the slices, the branch-vector partial rows) is placed in row `rank` of a zeroed (world, n)
+ * buffer, the buffer is all-reduced, and this call adds its rows in rank order: out[e] = sum over r = 0 .. world-1 of parts[r][e]. */
+extern "C" int macr_shard_fold_ranks(int world, long long n, const float *parts, float *out, void *stream) {
+    MACR_REQUIRE(world >= 1 && n >= 0, MACR_E_INVALID, "shard_fold_ranks: world=%d n=%lld", world, n);
+    MACR_REQUIRE(n == 0 || (parts && out), MACR_E_INVALID, "shard_fold_ranks: null pointer");
+    if (n == 0) return MACR_OK;
+    hipStream_t st = as_stream(stream);
+    k_fold_ranks<<<grid_for(n), 256, 0, st>>>(world, n, parts, out);
+    MACR_CHECK_LAUNCH("fold_ranks", st);
     return MACR_OK;
 }
 
@@ -3104,14 +3205,15 @@ static int shard_apply(int loss_kind, int B, int d, int n_users_loc, int n_items
                        int i_stride, const int32_t *u, const int32_t *i, const int32_t *j, float *P, float *Q, float *w,
                        float *wu, float *mP, float *vP, float *mQ, float *vQ, float *mw, float *vw, float *mwu, float *vwu,
                        float *gP, float *gQ, int32_t *touchedP, int32_t *touchedQ, const macr_hyper *hp,
-                       const macr_lazy_adam *lz, void *workspace, size_t workspace_bytes, void *stream) {
+                       const macr_lazy_adam *lz, void *workspace, size_t workspace_bytes, void *stream, bool det = false) {
+    // det: macr_shard_apply_det -- the workspace of macr_shard_workspace_bytes_det; every row one owner that sums in list order
     // (a rank may own no row of a table: that table's pointers may then be null -- no key names it, no Adam segment is built for it)
     MACR_REQUIRE(n_users_loc >= 0 && n_items_loc >= 0 && u_stride >= 1 && i_stride >= 1 && u && i && j && w && wu && mw && vw &&
                      mwu && vwu && ((P && mP && vP && gP && touchedP) || n_users_loc == 0) &&
                      ((Q && mQ && vQ && gQ && touchedQ) || n_items_loc == 0), MACR_E_INVALID, "shard_apply: bad argument");
     if (int e = validate_hyper(hp, "shard_apply")) return e;
     if (lz) if (int e = validate_lazy(lz, n_users_loc > 0, n_items_loc > 0, "shard_apply_lazy")) return e;
-    MACR_SHARD_COMMON("shard_apply");
+    MACR_SHARD_COMMON_AS("shard_apply", det);
     const int n = 3 * B;
     const Owned ou = {u_lo, u_stride, n_users_loc}, oi = {i_lo, i_stride, n_items_loc};
     k_shard_keys<<<grid_for(B), 256, 0, st>>>(B, ou, oi, u, i, j, ws.ska, ws.sva, ws.n_work,
@@ -3123,8 +3225,18 @@ static int shard_apply(int loss_kind, int B, int d, int n_users_loc, int n_items
     // longer runs -- the hot items -- go through gP/gQ by k_seg_sum).  MACR_SEG_UNFUSED=1: the segment reduce writes
     // every row, as before (A/B measurements, tests).
     const char *unfused = getenv("MACR_SEG_UNFUSED");
-    const bool indexed = (size_t)n <= kRefMaxRefs && !(unfused && unfused[0] == '1');
-    if (int e = indexed ? launch_seg_index(B, d, n_users_loc, n_items_loc, r, false, gP, gQ, touchedP, touchedQ, ws, st)
+    const bool indexed = !det && (size_t)n <= kRefMaxRefs && !(unfused && unfused[0] == '1');
+    if (det) {
+        // chunk sums of the cut runs to slots of their own, then ONE owner per row adds them in position order: no atomics, and
+        // no INDEX mode (whose long runs are summed by k_seg_sum with atomics) whatever MACR_SEG_UNFUSED says
+        const uint32_t key_end = (uint32_t)(n_users_loc + n_items_loc);
+        MACR_DISPATCH_LPR(d, (k_seg_reduce<LPR, true><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
+                                 n, n_users_loc, key_end, r.sk, r.sv, ws.stage, gP, gQ, touchedP, touchedQ, nullptr, nullptr, ws.cpart, nullptr)));
+        MACR_CHECK_LAUNCH("seg_reduce", st);
+        MACR_DISPATCH_LPR(d, (k_seg_fold<LPR><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
+                                 n, n_users_loc, key_end, r.sk, ws.cpart, gP, gQ, nullptr, nullptr)));
+        MACR_CHECK_LAUNCH("seg_fold", st);
+    } else if (int e = indexed ? launch_seg_index(B, d, n_users_loc, n_items_loc, r, false, gP, gQ, touchedP, touchedQ, ws, st)
                         : launch_seg_reduce(B, d, n_users_loc, n_items_loc, r, gP, gQ, touchedP, touchedQ, nullptr, nullptr, ws, st))
         return e;
     AdamArgs a;
@@ -3189,6 +3301,16 @@ extern "C" int macr_shard_apply_lazy(int loss_kind, int B, int d, int n_users_lo
     MACR_REQUIRE(lazy, MACR_E_INVALID, "shard_apply_lazy: lazy is null");
     return shard_apply(loss_kind, B, d, n_users_loc, n_items_loc, u_lo, u_stride, i_lo, i_stride, u, i, j, P, Q, w, wu, mP, vP, mQ, vQ,
                        mw, vw, mwu, vwu, gP, gQ, touchedP, touchedQ, hp, lazy, workspace, workspace_bytes, stream);
+}
+
+/* macr_shard_apply / macr_shard_apply_lazy (lazy != NULL) of the bit-reproducible sharded step */
+extern "C" int macr_shard_apply_det(int loss_kind, int B, int d, int n_users_loc, int n_items_loc, int u_lo, int u_stride, int i_lo,
+                                    int i_stride, const int32_t *u, const int32_t *i, const int32_t *j, float *P, float *Q, float *w,
+                                    float *wu, float *mP, float *vP, float *mQ, float *vQ, float *mw, float *vw, float *mwu,
+                                    float *vwu, float *gP, float *gQ, int32_t *touchedP, int32_t *touchedQ, const macr_hyper *hp,
+                                    const macr_lazy_adam *lazy, void *workspace, size_t workspace_bytes, void *stream) {
+    return shard_apply(loss_kind, B, d, n_users_loc, n_items_loc, u_lo, u_stride, i_lo, i_stride, u, i, j, P, Q, w, wu, mP, vP, mQ, vQ,
+                       mw, vw, mwu, vwu, gP, gQ, touchedP, touchedQ, hp, lazy, workspace, workspace_bytes, stream, true);
 }
 
 /* every row of the (local) tables brought to the current step: afterwards P, Q and the slots are what the per-step dense pass

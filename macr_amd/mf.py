@@ -249,11 +249,18 @@ class ShardedBPRMF(object):
     sharded = True
     _TRAIN = BPRMF._TRAIN
 
-    def __init__(self, args, data_config, device=None, seed=12345, layout="interleaved"):
-        if deterministic_from_env():
-            raise NotImplementedError("MACR_DETERMINISTIC=1 has no row-sharded step (--row_shard 1): the macr_shard_* entry points "
-                                      "have no deterministic mode; train unsharded or unset MACR_DETERMINISTIC")
+    def __init__(self, args, data_config, device=None, seed=12345, layout="interleaved", deterministic=None):
+        """deterministic: the bit-reproducible sharded step (sharded_train.HipBackend(deterministic=True)).  None:
+        MACR_SHARD_DETERMINISTIC=1 in the environment decides -- a switch of its own: its contract fixes the number of ranks, the
+        layout and the step form, which MACR_DETERMINISTIC's does not know."""
         from . import sharded_train, sharding
+        if deterministic is None:
+            deterministic = sharded_train.shard_deterministic_from_env()
+            if deterministic_from_env() and not deterministic:
+                raise NotImplementedError("MACR_DETERMINISTIC=1 does not cover the row-sharded step (--row_shard 1): its "
+                                          "bit-reproducible mode has a switch of its own, MACR_SHARD_DETERMINISTIC=1; set that, "
+                                          "train unsharded or unset MACR_DETERMINISTIC")
+        self.deterministic = bool(deterministic)
         self.n_users, self.n_items = data_config['n_users'], data_config['n_items']
         self.decay, self.emb_dim, self.lr, self.batch_size = args.regs, args.embed_size, args.lr, args.batch_size
         self.c, self.alpha, self.beta = args.c, args.alpha, args.beta
@@ -292,7 +299,7 @@ class ShardedBPRMF(object):
                 raise NotImplementedError("a row-sharded model trains with one loss kind per run")
             P, Q, w, wu = self._init
             self._models[kind] = sharded_train.RowShardedMF(
-                None, None, w, wu, sharded_train.HipBackend(kind, self.d_pad, self._hyper, self.device), rank=self.rank,
+                None, None, w, wu, sharded_train.HipBackend(kind, self.d_pad, self._hyper, self.device, self.deterministic), rank=self.rank,
                 world=self.world, shards=(P, Q, self.n_users, self.n_items), layout=self._layout)
         return self._models[kind]
 

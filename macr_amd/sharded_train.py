@@ -19,7 +19,12 @@ batch itself is a few MB.  So the rows of P and Q (with their Adam slots and gra
 All three collectives are latency-class messages on xGMI (12.6 MB + 0.5 MB + 8 KB at B = 8192, d = 128).  The math is
 the single-GPU step's (macr_mf_train_step) up to summation order, for all three loss kinds (`normalbce` has no (B,B)
 term and no branch vectors: steps 2-4 are one kernel and there is ONE collective per step); `backend` is the device half (HIP: the macr_shard_*
-entry points of include/macr_hip.h; the CPU tests plug the oracle in its place)."""
+entry points of include/macr_hip.h; the CPU tests plug the oracle in its place).
+
+Bit-reproducible mode (HipBackend(deterministic=True); MACR_SHARD_DETERMINISTIC=1 for the CLI): backward and apply run the
+macr_shard_*_det entry points (one owner per gradient row, branch-vector partial rows folded in block order), and the split
+step's two sums over the ranks whose operands overlap travel as one row per rank and are folded in rank order
+(RowShardedMF._all_reduce_folded), so that no result depends on the order a collective adds in.  Contract: include/macr_hip.h."""
 import ctypes
 import os
 
@@ -28,6 +33,12 @@ import torch.distributed as dist
 
 from . import sharding
 from ._lib import is_pair_loss
+
+def shard_deterministic_from_env():
+    """MACR_SHARD_DETERMINISTIC=1 in the environment: the row-sharded step runs in its bit-reproducible mode (include/macr_hip.h,
+    macr_shard_*_det).  A switch of its own, with its own contract: MACR_DETERMINISTIC covers the unsharded steps."""
+    return os.environ.get("MACR_SHARD_DETERMINISTIC", "") == "1"
+
 
 def row_range(n_rows, rank, world):
     """Contiguous, balanced [lo, hi) of the rows rank owns (same rule as the evaluator's item shards)."""
@@ -93,16 +104,21 @@ class HipBackend(object):
     """Device half on the MI355X: thin calls into libmacr_hip.so (no fallback)."""
     lazy_capable = True                 # the lazy dense Adam pass (include/macr_hip.h: macr_lazy_adam) exists on this backend
 
-    def __init__(self, kind, d, hyper, device):
+    def __init__(self, kind, d, hyper, device, deterministic=False):
+        """deterministic: the bit-reproducible step -- the workspace of macr_shard_workspace_bytes_det, backward / backward_slice /
+        apply through the _det entry points; RowShardedMF takes the mode from here (and folds the split step's cross-rank sums
+        in rank order: fold_ranks)"""
         from . import _lib, ops
         self._lib, self.ops, self.kind, self.d, self.hyper, self.device = _lib, ops, kind, d, hyper, device
+        self.deterministic = bool(deterministic)
         self.ws, self.cap = None, 0
         self.adam_pow = torch.tensor([hyper.beta1, hyper.beta2], dtype=torch.float32, device=device)
         self.losses = torch.zeros(3, dtype=torch.float32, device=device)
 
     def _reserve(self, B):
         if B > self.cap:
-            n = self._lib.lib().macr_shard_workspace_bytes(B, self.d)
+            L = self._lib.lib()
+            n = (L.macr_shard_workspace_bytes_det if self.deterministic else L.macr_shard_workspace_bytes)(B, self.d)
             if n == 0:
                 raise self._lib.MacrError(self._lib.E_UNSUPPORTED, "embed_size %d not in {32,64,128,256}" % self.d)
             self.ws, self.cap = torch.empty(n, dtype=torch.uint8, device=self.device), B
@@ -174,10 +190,10 @@ class HipBackend(object):
         o, L = self.ops, self._lib.lib()
         B = rows3.shape[1]
         ptr, nbytes = ctypes.c_void_p(), ctypes.c_size_t()
-        self._lib.check(L.macr_shard_backward(self.kind, B, self.d, o._ptr(rows3), o._ptr(shard.w), o._ptr(shard.wu),
-                                              o._ptr(self.adam_pow), ctypes.byref(self.hyper), o._ptr(self.losses),
-                                              ctypes.byref(ptr), ctypes.byref(nbytes), o._ptr(self.ws), self.ws.numel(),
-                                              o._stream()))
+        call = L.macr_shard_backward_det if self.deterministic else L.macr_shard_backward
+        self._lib.check(call(self.kind, B, self.d, o._ptr(rows3), o._ptr(shard.w), o._ptr(shard.wu),
+                             o._ptr(self.adam_pow), ctypes.byref(self.hyper), o._ptr(self.losses),
+                             ctypes.byref(ptr), ctypes.byref(nbytes), o._ptr(self.ws), self.ws.numel(), o._stream()))
         if not nbytes.value:
             return self.losses, None                        # normalbce, bpr: no branch vectors
         return self.losses, self._view(ptr, nbytes)         # losses; branch-vector partial rows (broadcast from rank 0)
@@ -230,11 +246,28 @@ class HipBackend(object):
         n = rows3_slice.shape[1]
         stage = torch.empty((3, n, self.d), dtype=torch.float32, device=self.device)
         ptr, nbytes = ctypes.c_void_p(), ctypes.c_size_t()
-        self._lib.check(L.macr_shard_backward_slice(self.kind, B, self.d, t0, n, o._ptr(rows3_slice), o._ptr(shard.w), o._ptr(shard.wu),
-                                                    o._ptr(self.adam_pow), ctypes.byref(self.hyper), o._ptr(self.losses), o._ptr(stage),
-                                                    ctypes.byref(ptr), ctypes.byref(nbytes), o._ptr(self.ws), self.ws.numel(),
-                                                    o._stream()))
+        call = L.macr_shard_backward_slice_det if self.deterministic else L.macr_shard_backward_slice
+        self._lib.check(call(self.kind, B, self.d, t0, n, o._ptr(rows3_slice), o._ptr(shard.w), o._ptr(shard.wu),
+                             o._ptr(self.adam_pow), ctypes.byref(self.hyper), o._ptr(self.losses), o._ptr(stage),
+                             ctypes.byref(ptr), ctypes.byref(nbytes), o._ptr(self.ws), self.ws.numel(), o._stream()))
         return self.losses, stage, self._view(ptr, nbytes)
+
+    # ---- the deterministic split step's sum over the ranks of a workspace region that several ranks fill at the SAME indices:
+    # the region goes into row `rank` of a zeroed (world, n) buffer (rank_rows), the caller all-reduces the buffer -- every
+    # element is x + 0 + .. + 0, exact in whatever order the collective adds -- and fold_ranks adds its rows in rank order
+    # back into the region (macr_shard_fold_ranks)
+    def rank_rows(self, region, rank, world):
+        key = ("rank_rows", world, region.numel())
+        rows = self.__dict__.get(key)
+        if rows is None:
+            rows = self.__dict__[key] = torch.empty((world, region.numel()), dtype=torch.float32, device=self.device)
+        rows.zero_()
+        rows[rank].copy_(region)
+        return rows
+
+    def fold_ranks(self, rows, region):
+        o = self.ops
+        self._lib.check(self._lib.lib().macr_shard_fold_ranks(rows.shape[0], region.numel(), o._ptr(rows), o._ptr(region), o._stream()))
 
     def stage_rows(self, B):
         """(3*B, d) view of the staging buffer macr_shard_apply reads (row role*B + t)"""
@@ -252,7 +285,9 @@ class HipBackend(object):
                 o._ptr(shard.gP), o._ptr(shard.gQ), o._ptr(shard.tP), o._ptr(shard.tQ), ctypes.byref(self.hyper))
         tail = (o._ptr(self.ws), self.ws.numel(), o._stream())
         lz = self._lazy(shard)
-        if lz is not None:
+        if self.deterministic:
+            self._lib.check(L.macr_shard_apply_det(*(head + (ctypes.byref(lz) if lz is not None else None,) + tail)))
+        elif lz is not None:
             self._lib.check(L.macr_shard_apply_lazy(*(head + (ctypes.byref(lz),) + tail)))
         else:
             self._lib.check(L.macr_shard_apply(*(head + tail)))
@@ -301,6 +336,7 @@ class RowShardedMF(object):
         self.tP = torch.zeros(self._P.shape[0], dtype=torch.int32, device=dev)
         self.tQ = torch.zeros(self._Q.shape[0], dtype=torch.int32, device=dev)
         self.backend = backend
+        self.deterministic = bool(getattr(backend, "deterministic", False))     # (the mode is the backend's: it sized the workspace)
         # lazy dense Adam: row stamps + the library's step counter / lr_t ring; `_stale` = some row is behind the current step
         if lazy_period is None:
             env = os.environ.get("MACR_LAZY_ADAM", "")
@@ -366,6 +402,13 @@ class RowShardedMF(object):
             self._timed(name, via_host)
         else:
             self._timed(name, lambda: dist.all_reduce(t, group=self.group))
+
+    def _all_reduce_folded(self, region, name):
+        """sum over the ranks of a region every rank fills at the same indices, in RANK order whatever order the collective adds
+        in (HipBackend.rank_rows): the deterministic split step's loss partials and branch-vector partial rows"""
+        rows = self.backend.rank_rows(region, self.rank, self.world)
+        self._all_reduce(rows, name)
+        self.backend.fold_ranks(rows, region)
 
     def _broadcast(self, t, src=0, name="broadcast"):
         if self.world == 1 and not sharding.force_collectives():
@@ -441,6 +484,8 @@ class RowShardedMF(object):
         (B,B) row blocks.  Per rank and step: all-to-all of the 3B/W rows its slice needs (from their owners), an all-reduce of
         the forward scalars (7 floats per position), the all-reduce of the (B,B) partial sums, an all-reduce of the
         branch-vector gradient partials, all-to-all of the 3B/W gradient rows back to the owners, then the local Adam pass.
+        Deterministic backend: the two all-reduces whose operands overlap (forward region, branch rows) carry one row per rank
+        and are folded in rank order (_all_reduce_folded): W times their bytes on the wire, still latency-class messages.
         counts: the (W, W) table of route() as python ints when the caller knows the batch on the host (no synchronisation)."""
         be, W, B = self.backend, self.world, u.numel()
         cnt, send_ref, recv_ref, rows = self.route(u, i, j)
@@ -477,12 +522,20 @@ class RowShardedMF(object):
         rows3[slot] = recv
         rows3 = rows3.view(3, n, d)
         # 2. forward of the slice; its scalars and loss partials summed into the whole batch's
-        self._all_reduce(be.forward_slice(self, B, t0, rows3), "fwd")
+        # (deterministic: the loss partials of the slices land on the same indices -- W real addends per element in an order the
+        # collective picks -- so the region travels as one row per rank and is folded in rank order; so do the branch rows below)
+        if self.deterministic:
+            self._all_reduce_folded(be.forward_slice(self, B, t0, rows3), "fwd")
+        else:
+            self._all_reduce(be.forward_slice(self, B, t0, rows3), "fwd")
         # 3. my (B,B) row blocks; partial row / column sums over the ranks
         self._all_reduce(be.bxb(B, self.rank, W), "partials")
         # 4. backward of the slice; branch-vector gradient partials summed (identical on every rank afterwards)
         losses, stage, branch = be.backward_slice(self, B, t0, rows3)
-        self._all_reduce(branch, "branch")
+        if self.deterministic:
+            self._all_reduce_folded(branch, "branch")
+        else:
+            self._all_reduce(branch, "branch")
         # 5. gradient rows back to the owners, into the staging rows macr_shard_apply reads
         back = torch.empty((n_send, d), dtype=self._P.dtype, device=self._P.device)
         self._all_to_all(back, stage.view(3 * n, d)[slot].contiguous(), send_counts, recv_counts, "grads_a2a")
