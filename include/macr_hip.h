@@ -397,6 +397,59 @@ int macr_shard_apply_det(int loss_kind, int B, int d, int n_users_loc, int n_ite
                          float *gP, float *gQ, int32_t *touchedP, int32_t *touchedQ, const macr_hyper *hp,
                          const macr_lazy_adam *lazy, void *workspace, size_t workspace_bytes, void *stream);
 int macr_shard_fold_ranks(int world, long long n, const float *parts, float *out, void *stream);
+/* ---------------------------------------------------------------------------
+ * The rank-count-invariant row-sharded step (additive, abi 16; host switch MACR_SHARD_INVARIANT=1, macr_amd/sharded_train.py).
+ * CONTRACT: with the _inv entry points in place of their counterparts, the split step's slices taken from macr_shard_slice_inv
+ * and its regions summed over the ranks with plain sums, the per-step losses on every rank, P, Q, mP, vP, mQ, vQ reassembled
+ * from the shards after a flush, w, wu and their slots and adam_pow are a function only of the batches, the hyper-parameters,
+ * the library build and the device model.  They are bit-identical across 1 <= world <= 16, the interleaved and range row
+ * layouts, the replicated and split step forms, lazy periods (compared after a flush) and the order in which any collective
+ * adds its operands.  It implies everything the _det contract promises.  NOT promised: equal bits with macr_mf_train_step, with
+ * the plain or the _det sharded entry points, or -- the losses apart -- between the flushes of a lazy sequence.  The results
+ * differ from the plain entry points' by fp32 rounding only.  (A sum over the ranks turns -0 into +0 when world > 1; the one
+ * reader of a zero's sign is the column flag stored with sig(su), which is zero only for a user-branch logit below -103.)
+ * How: (1) a gradient row's two-level sum is cut at run_start + k * CH, run_start = the lower bound of the row's key in the
+ * rank's sorted reference list and CH = min(d / 4, 16): its shape depends on the number of references alone, and their order
+ * is the reference order on every rank (the sort is stable).  (2) The slices of the split step are cut at multiples of 32
+ * positions -- the largest rows-per-block of the forward and backward kernels -- so that block k of a slice is block
+ * t0 / (1024 / d) + k of the whole batch and sums the same positions; loss partials and per-block branch-vector rows are
+ * written THERE, into zeroed regions: every element of a sum over the ranks is x + 0 + .. + 0, and every rank folds the complete
+ * set of block rows in block order, as the replicated step and world 1 do.  Everything else is the world-1 computation by
+ * construction (rows3 and the (B,B) partials are disjoint across the ranks; the Adam passes have one owner per row).
+ *   macr_shard_workspace_bytes_inv  = macr_shard_workspace_bytes_det: the plain layout as a prefix, then 2 * ceil(3B / CH) rows of
+ *       d floats (chunk sums: at most two chunks of runs longer than CH begin in a window of CH positions) and one 2*d row per
+ *       backward block (min(ceil(B / (1024 / d)), 4096) rows).
+ *   macr_shard_slice_inv   (host only) [t0, t1) of rank: cuts at ceil(B / 32) * rank / world * 32, clipped to B -- the same for
+ *       every d; a slice may be empty.  LIMIT of the split form: one backward block per 1024 / d positions and at most 4096
+ *       blocks, B <= 4096 * 1024 / d (beyond it the launch grid-strides, which changes the positions a block sums): refused with
+ *       MACR_E_UNSUPPORTED here and by the three calls below, before any device work.  The replicated form serves such a batch.
+ *   macr_shard_forward_slice_inv, macr_shard_backward_slice_inv   arguments and answers of the plain calls; a slice not cut as
+ *       above is MACR_E_INVALID.  The backward call returns the block-row region ((dev) fp32[ceil(B / (1024 / d))][2][d], zero
+ *       outside the slice's blocks) instead of folded rows: sum it over the ranks, then
+ *   macr_shard_branch_fold_inv   folds the region in block order into the rows macr_shard_apply_inv reads.
+ *   macr_shard_backward_inv   the replicated step's backward: arguments and answers of macr_shard_backward.
+ *   macr_shard_apply_inv   arguments of macr_shard_apply_lazy; lazy may be NULL (the dense pass).  No atomics; gP, gQ and the row
+ *       flags are clean on return.
+ * -------------------------------------------------------------------------*/
+size_t macr_shard_workspace_bytes_inv(int B, int d);
+int macr_shard_slice_inv(int B, int d, int rank, int world, int *t0, int *t1);
+int macr_shard_backward_inv(int loss_kind, int B, int d, const float *rows3, const float *w, const float *wu,
+                            float *adam_pow, const macr_hyper *hp, float *losses, void **branch_grads,
+                            size_t *branch_bytes, void *workspace, size_t workspace_bytes, void *stream);
+int macr_shard_forward_slice_inv(int loss_kind, int B, int d, int t0, int n, const float *rows3_slice, const float *w,
+                                 const float *wu, void **region, size_t *region_bytes, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+int macr_shard_backward_slice_inv(int loss_kind, int B, int d, int t0, int n, const float *rows3_slice, const float *w,
+                                  const float *wu, float *adam_pow, const macr_hyper *hp, float *losses,
+                                  float *stage_slice, void **branch_grads, size_t *branch_bytes, void *workspace,
+                                  size_t workspace_bytes, void *stream);
+int macr_shard_branch_fold_inv(int B, int d, void *workspace, size_t workspace_bytes, void *stream);
+int macr_shard_apply_inv(int loss_kind, int B, int d, int n_users_loc, int n_items_loc, int u_lo, int u_stride, int i_lo,
+                         int i_stride, const int32_t *u, const int32_t *i, const int32_t *j,
+                         float *P_loc, float *Q_loc, float *w, float *wu,
+                         float *mP, float *vP, float *mQ, float *vQ, float *mw, float *vw, float *mwu, float *vwu,
+                         float *gP, float *gQ, int32_t *touchedP, int32_t *touchedQ, const macr_hyper *hp,
+                         const macr_lazy_adam *lazy, void *workspace, size_t workspace_bytes, void *stream);
 /* every row of both tables brought to the current step (n_rows_p / n_rows_q: rows of the local tables) */
 int macr_lazy_flush(int d, long long n_rows_p, long long n_rows_q, float *P, float *Q, float *mP, float *vP, float *mQ,
                     float *vQ, const macr_hyper *hp, const macr_lazy_adam *lazy, void *stream);

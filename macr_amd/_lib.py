@@ -81,6 +81,13 @@ SIGNATURES = {
     "macr_shard_backward_slice_det": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, ctypes.POINTER(Hyper), _p, _p, _p, _p, _p, _z, _p]),
     "macr_shard_apply_det": (_i, [_i] * 9 + [_p] * 3 + [_p] * 12 + [_p] * 4 + [ctypes.POINTER(Hyper), ctypes.POINTER(LazyAdam), _p, _z, _p]),
     "macr_shard_fold_ranks": (_i, [_i, _ll, _p, _p, _p]),
+    "macr_shard_workspace_bytes_inv": (_z, [_i, _i]),
+    "macr_shard_slice_inv": (_i, [_i, _i, _i, _i, _p, _p]),
+    "macr_shard_backward_inv": (_i, [_i, _i, _i, _p, _p, _p, _p, ctypes.POINTER(Hyper), _p, _p, _p, _p, _z, _p]),
+    "macr_shard_forward_slice_inv": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
+    "macr_shard_backward_slice_inv": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, ctypes.POINTER(Hyper), _p, _p, _p, _p, _p, _z, _p]),
+    "macr_shard_branch_fold_inv": (_i, [_i, _i, _p, _z, _p]),
+    "macr_shard_apply_inv": (_i, [_i] * 9 + [_p] * 3 + [_p] * 12 + [_p] * 4 + [ctypes.POINTER(Hyper), ctypes.POINTER(LazyAdam), _p, _z, _p]),
     "macr_lazy_flush": (_i, [_i, _ll, _ll] + [_p] * 6 + [ctypes.POINTER(Hyper), ctypes.POINTER(LazyAdam), _p]),
     "macr_sample_triples": (_i, [ctypes.c_uint64, ctypes.c_uint64, _i, _i, _p, _i, _p, _p, _p, _p]),
     "macr_sample_triples_many": (_i, [ctypes.c_uint64, ctypes.c_uint64, _i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p]),

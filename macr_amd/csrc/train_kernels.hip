@@ -1793,6 +1793,106 @@ __global__ __launch_bounds__(256) void k_seg_fold(int n, int n_users, uint32_t k
     }
 }
 
+// RUN-ALIGNED two-level row sums (MACR_SHARD_INVARIANT, include/macr_hip.h: macr_shard_apply_inv).  k_seg_reduce<LPR, true> cuts
+// a run at multiples of CH of the LIST position, so where a run lies in the list -- which other rows the rank owns -- shapes its
+// sum.  Here the chunks of a run begin at run_start + k * CH (run_start: the lower bound of the key in the sorted list): the
+// shape of a row's sum is a function of the run's length alone, and the order inside a run is the reference order everywhere
+// (the sort is stable).  A run of at most CH references is stored directly; a longer one stores its chunk sums to cpart and
+// k_seg_fold_inv adds them.  Slot of the chunk that begins at position q: 2 * (q / CH) + (q == run_start).  Heads of ONE run
+// are CH apart, so a window of CH positions holds at most one head per run; a run with several chunks (longer than CH) whose
+// head lies in the window either began before the window -- one run at most -- or begins inside it and leaves it -- one run at
+// most, the last that begins there: at most two such chunks per window, bit 0 tells them apart, and the 2 * ceil(3B / CH) rows
+// of the deterministic workspace suffice.  No atomics.
+template <int LPR>
+__global__ __launch_bounds__(256) void k_seg_reduce_inv(int n, int n_users, uint32_t key_end, const uint32_t *__restrict__ sk,
+                                                        const uint32_t *__restrict__ sv, const float *__restrict__ stage,
+                                                        float *gU, float *gI, int32_t *tU, int32_t *tI, float *__restrict__ cpart) {
+    constexpr int d = 4 * LPR, RPB = RowGroup<LPR>::kRowsPerBlock, CH = LPR < 16 ? LPR : 16;
+    RowGroup<LPR> g;
+    const long long p = (long long)blockIdx.x * RPB + g.slot;
+    const bool in = p < n;
+    const int lane = threadIdx.x & 63, gbase = lane - g.sub;
+    uint32_t ks = 0xffffffffu, vs = 0u;
+    if (in && g.sub < CH && p + g.sub < n) { ks = sk[p + g.sub]; vs = sv[p + g.sub]; }
+    const uint32_t key0 = __shfl(ks, gbase, kWave);
+    const uint64_t eq = __ballot(in && g.sub < CH && ks == key0);
+    const uint64_t gmask = LPR == 64 ? ~0ull : (((1ull << LPR) - 1ull) << gbase);
+    const int len = __popcll(eq & gmask);                           // equal keys are contiguous from p (sorted); <= CH
+    if (!in || key0 >= key_end) return;                             // keys >= key_end: not this rank's rows
+    long long rs = p;                                               // run_start: first position that holds key0
+    if (p > 0 && sk[p - 1] == key0) {
+        if (p < CH || sk[p - CH] != key0) return;                   // 0 < p - run_start < CH: inside a chunk
+        long long hi = p - CH, step = CH;                           // sk[hi] == key0; gallop back, then bisect
+        while (hi - step >= 0 && sk[hi - step] == key0) { hi -= step; step *= 2; }
+        long long lo = hi - step >= 0 ? hi - step : -1;             // sk[lo] != key0, or lo == -1
+        while (lo + 1 < hi) {
+            const long long mid = (lo + hi) >> 1;
+            if (sk[mid] == key0) hi = mid; else lo = mid;
+        }
+        rs = hi;
+        if ((p - rs) % CH != 0) return;
+    }
+    const bool multi = p != rs || (len == CH && p + CH < n && sk[p + CH] == key0);
+    const bool is_user = key0 < (uint32_t)n_users;
+    const size_t row = is_user ? key0 : key0 - (uint32_t)n_users;
+    float4 acc = make_float4(0, 0, 0, 0);
+    int k = 0;
+    for (; k + 4 <= len; k += 4) {
+        const uint32_t r0 = __shfl(vs, gbase + k, kWave), r1 = __shfl(vs, gbase + k + 1, kWave);
+        const uint32_t r2 = __shfl(vs, gbase + k + 2, kWave), r3 = __shfl(vs, gbase + k + 3, kWave);
+        const float4 x0 = ld4(stage + (size_t)r0 * d + 4 * g.sub), x1 = ld4(stage + (size_t)r1 * d + 4 * g.sub);
+        const float4 x2 = ld4(stage + (size_t)r2 * d + 4 * g.sub), x3 = ld4(stage + (size_t)r3 * d + 4 * g.sub);
+        acc = add4(add4(add4(add4(acc, x0), x1), x2), x3);
+    }
+    for (; k < len; ++k) {
+        const uint32_t r = __shfl(vs, gbase + k, kWave);
+        acc = add4(acc, ld4(stage + (size_t)r * d + 4 * g.sub));
+    }
+    if (multi) st4(cpart + (size_t)(2 * (p / CH) + (p == rs)) * d + 4 * g.sub, acc);
+    else st4((is_user ? gU : gI) + row * d + 4 * g.sub, acc);
+    int32_t *tf = is_user ? tU : tI;
+    if (g.sub == 0 && p == rs && tf) tf[row] = 1;
+}
+
+// Second level: the group at the FIRST reference of a run longer than CH owns the row.  It finds the run's end by galloping +
+// bisection and adds the ceil(len / CH) chunk sums in chunk order through four interleaved accumulators, ((a0 + a1) + (a2 + a3)):
+// chunk 0 and every fourth after it in a0, chunks 1, 5, .. in a1, and so on -- a shape that depends on the run's length alone.
+template <int LPR>
+__global__ __launch_bounds__(256) void k_seg_fold_inv(int n, int n_users, uint32_t key_end, const uint32_t *__restrict__ sk,
+                                                      const float *__restrict__ cpart, float *gU, float *gI) {
+    constexpr int d = 4 * LPR, RPB = RowGroup<LPR>::kRowsPerBlock, CH = LPR < 16 ? LPR : 16;
+    RowGroup<LPR> g;
+    const long long p = (long long)blockIdx.x * RPB + g.slot;
+    if (p >= n) return;
+    const uint32_t key = sk[p];
+    const uint32_t prev = p > 0 ? sk[p - 1] : 0xffffffffu;
+    if (key >= key_end || key == prev) return;                     // not the first reference of one of this rank's rows
+    if (p + CH >= n || sk[p + CH] != key) return;                  // at most CH references: k_seg_reduce_inv stored the row
+    long long lo = p + CH, step = CH;                              // sk[lo] == key
+    while (lo + step < n && sk[lo + step] == key) { lo += step; step *= 2; }
+    long long hi = lo + step < n ? lo + step : n;                  // sk[hi] != key, or hi == n
+    while (lo + 1 < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (sk[mid] == key) lo = mid; else hi = mid;
+    }
+    const long long nc = (lo - p) / CH;                            // chunks 1 .. nc follow the first (lo: the last reference)
+    const float *src = cpart + 4 * g.sub;
+    auto part = [&](long long k) { return ld4(src + (size_t)(2 * ((p + k * CH) / CH)) * d); };
+    float4 a0 = ld4(src + (size_t)(2 * (p / CH) + 1) * d);
+    float4 a1 = make_float4(0, 0, 0, 0), a2 = a1, a3 = a1;
+    long long k = 1;
+#pragma unroll 2
+    for (; k + 3 <= nc; k += 4) {
+        const float4 x1 = part(k), x2 = part(k + 1), x3 = part(k + 2), x0 = part(k + 3);
+        a1 = add4(a1, x1); a2 = add4(a2, x2); a3 = add4(a3, x3); a0 = add4(a0, x0);
+    }
+    if (k <= nc) a1 = add4(a1, part(k));
+    if (k + 1 <= nc) a2 = add4(a2, part(k + 1));
+    if (k + 2 <= nc) a3 = add4(a3, part(k + 2));
+    const bool is_user = key < (uint32_t)n_users;
+    st4((is_user ? gU : gI) + (size_t)(is_user ? key : key - (uint32_t)n_users) * d + 4 * g.sub, add4(add4(a0, a1), add4(a2, a3)));
+}
+
 // The same de-duplication for a step whose Adam pass follows at once (adam_block INDEXED): nothing is summed for a row
 // with at most kRefRun references -- its flag names them, (count << kRefShift) | position of the first, and the pass
 // sums them.  One THREAD per position looks for the first reference of a row (k_seg_reduce spends a lane group per
@@ -3205,8 +3305,10 @@ static int shard_apply(int loss_kind, int B, int d, int n_users_loc, int n_items
                        int i_stride, const int32_t *u, const int32_t *i, const int32_t *j, float *P, float *Q, float *w,
                        float *wu, float *mP, float *vP, float *mQ, float *vQ, float *mw, float *vw, float *mwu, float *vwu,
                        float *gP, float *gQ, int32_t *touchedP, int32_t *touchedQ, const macr_hyper *hp,
-                       const macr_lazy_adam *lz, void *workspace, size_t workspace_bytes, void *stream, bool det = false) {
+                       const macr_lazy_adam *lz, void *workspace, size_t workspace_bytes, void *stream, bool det = false,
+                       bool inv = false) {
     // det: macr_shard_apply_det -- the workspace of macr_shard_workspace_bytes_det; every row one owner that sums in list order
+    // inv (implies det): macr_shard_apply_inv -- the same workspace; the two-level sums cut at the RUN's start (k_seg_reduce_inv)
     // (a rank may own no row of a table: that table's pointers may then be null -- no key names it, no Adam segment is built for it)
     MACR_REQUIRE(n_users_loc >= 0 && n_items_loc >= 0 && u_stride >= 1 && i_stride >= 1 && u && i && j && w && wu && mw && vw &&
                      mwu && vwu && ((P && mP && vP && gP && touchedP) || n_users_loc == 0) &&
@@ -3226,7 +3328,16 @@ static int shard_apply(int loss_kind, int B, int d, int n_users_loc, int n_items
     // every row, as before (A/B measurements, tests).
     const char *unfused = getenv("MACR_SEG_UNFUSED");
     const bool indexed = !det && (size_t)n <= kRefMaxRefs && !(unfused && unfused[0] == '1');
-    if (det) {
+    if (inv) {
+        // as below, with chunks that begin at the run's start: the shape of a row's sum depends on its references alone
+        const uint32_t key_end = (uint32_t)(n_users_loc + n_items_loc);
+        MACR_DISPATCH_LPR(d, (k_seg_reduce_inv<LPR><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
+                                 n, n_users_loc, key_end, r.sk, r.sv, ws.stage, gP, gQ, touchedP, touchedQ, ws.cpart)));
+        MACR_CHECK_LAUNCH("seg_reduce_inv", st);
+        MACR_DISPATCH_LPR(d, (k_seg_fold_inv<LPR><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
+                                 n, n_users_loc, key_end, r.sk, ws.cpart, gP, gQ)));
+        MACR_CHECK_LAUNCH("seg_fold_inv", st);
+    } else if (det) {
         // chunk sums of the cut runs to slots of their own, then ONE owner per row adds them in position order: no atomics, and
         // no INDEX mode (whose long runs are summed by k_seg_sum with atomics) whatever MACR_SEG_UNFUSED says
         const uint32_t key_end = (uint32_t)(n_users_loc + n_items_loc);
@@ -3311,6 +3422,122 @@ extern "C" int macr_shard_apply_det(int loss_kind, int B, int d, int n_users_loc
                                     const macr_lazy_adam *lazy, void *workspace, size_t workspace_bytes, void *stream) {
     return shard_apply(loss_kind, B, d, n_users_loc, n_items_loc, u_lo, u_stride, i_lo, i_stride, u, i, j, P, Q, w, wu, mP, vP, mQ, vQ,
                        mw, vw, mwu, vwu, gP, gQ, touchedP, touchedQ, hp, lazy, workspace, workspace_bytes, stream, true);
+}
+
+/* ---- the rank-count-invariant row-sharded step (MACR_SHARD_INVARIANT, include/macr_hip.h: macr_shard_*_inv) ----------------------
+ * The deterministic step with its two leaks of the cluster shape closed: the two-level row sums are cut at the run's start
+ * (k_seg_reduce_inv / k_seg_fold_inv), and the split step's slices are cut at multiples of kInvAlign positions and write their
+ * loss partials and per-block branch-vector rows at the block's index in the WHOLE batch, so that a plain sum over the ranks is
+ * x + 0 + .. + 0 and every rank folds the complete set of block rows in block order -- what the replicated step and world 1 do. */
+namespace macr {
+constexpr int kInvAlign = 32;            // the largest rows-per-block of k_pair_fwd / k_pair_bwd_stage (256 / (d / 4) at d = 32)
+// The split form needs one backward block per 1024 / d positions -- the launch caps at 4096 blocks and grid-strides beyond,
+// which changes the positions a block sums: such a batch (B > 4096 * 1024 / d) is refused; the replicated form serves it.
+// (an unsupported d is refused by the caller's own check)
+static inline bool inv_split_serves(int B, int d) { return !dim_supported(d) || ((long long)B + 1024 / d - 1) / (1024 / d) <= 4096; }
+static inline bool inv_slice_aligned(int B, int t0, int n) {
+    return t0 % kInvAlign == 0 && (t0 + n == B || (t0 + n) % kInvAlign == 0);
+}
+}  // namespace macr
+
+extern "C" size_t macr_shard_workspace_bytes_inv(int B, int d) { return macr_shard_workspace_bytes_det(B, d); }
+
+extern "C" int macr_shard_slice_inv(int B, int d, int rank, int world, int *t0, int *t1) {
+    MACR_REQUIRE(B > 0 && dim_supported(d) && world >= 1 && rank >= 0 && rank < world && t0 && t1, MACR_E_INVALID, "shard_slice_inv: bad argument");
+    MACR_REQUIRE(inv_split_serves(B, d), MACR_E_UNSUPPORTED, "shard_slice_inv: B=%d needs more than 4096 blocks of %d positions", B, 1024 / d);
+    const long long nb = ((long long)B + kInvAlign - 1) / kInvAlign;
+    const long long a = nb * rank / world * kInvAlign, b = nb * (rank + 1) / world * kInvAlign;
+    *t0 = (int)(a < B ? a : B);
+    *t1 = (int)(b < B ? b : B);
+    return MACR_OK;
+}
+
+extern "C" int macr_shard_backward_inv(int loss_kind, int B, int d, const float *rows3, const float *w, const float *wu,
+                                       float *adam_pow, const macr_hyper *hp, float *losses, void **branch_grads,
+                                       size_t *branch_bytes, void *workspace, size_t workspace_bytes, void *stream) {
+    // (one partial row per block, folded in block order: nothing in it knows the rank or the world)
+    return shard_backward(true, loss_kind, B, d, rows3, w, wu, adam_pow, hp, losses, branch_grads, branch_bytes, workspace,
+                          workspace_bytes, stream);
+}
+
+/* macr_shard_forward_slice with the slice's loss partials at the blocks' indices in the whole batch */
+extern "C" int macr_shard_forward_slice_inv(int loss_kind, int B, int d, int t0, int n, const float *rows3_slice, const float *w,
+                                            const float *wu, void **region, size_t *region_bytes, void *workspace,
+                                            size_t workspace_bytes, void *stream) {
+    MACR_REQUIRE(loss_kind == MACR_LOSS_RUBIBCEBOTH || loss_kind == MACR_LOSS_RUBIBCE, MACR_E_UNSUPPORTED,
+                 "shard_forward_slice_inv: loss_kind=%d (the split step serves the losses with a (B,B) term)", loss_kind);
+    MACR_REQUIRE(w && wu && t0 >= 0 && n >= 0 && t0 + n <= B && (n == 0 || rows3_slice), MACR_E_INVALID, "shard_forward_slice_inv: bad argument");
+    MACR_REQUIRE(inv_slice_aligned(B, t0, n), MACR_E_INVALID, "shard_forward_slice_inv: slice [%d, %d) not cut at multiples of %d", t0, t0 + n, kInvAlign);
+    MACR_REQUIRE(inv_split_serves(B, d), MACR_E_UNSUPPORTED, "shard_forward_slice_inv: B=%d needs more than 4096 blocks of %d positions", B, 1024 / d);
+    MACR_SHARD_COMMON_AS("shard_forward_slice_inv", true);
+    char *lo = reinterpret_cast<char *>(ws.fwd), *hi = reinterpret_cast<char *>(ws.lpart);      // fwd | part | part2
+    fill_words(lo, (size_t)(hi - lo) / 4, 0u, st);
+    fill_words(ws.gw, (size_t)kBranchSlots * 2 * d, 0u, st);
+    if (region) *region = lo;
+    if (region_bytes) *region_bytes = (size_t)(hi - lo);
+    if (n > 0) {
+        k_iota3<<<grid_for(n), 256, 0, st>>>(n, sw.iota);
+        PendingAdam none = {};
+        const int lpr = d / 4, rpb = 256 / lpr, nblk = (n + rpb - 1) / rpb;             // t0 / rpb + nblk <= ws.nblk_pair
+        MACR_DISPATCH_LPR(d, (k_pair_fwd<LPR, 0><<<nblk, 256, 0, st>>>(n, ws.Bp, sw.iota, sw.iota + n, sw.iota + 2 * (size_t)n, rows3_slice,
+                                                                          rows3_slice + (size_t)n * d, w, wu, ws.fwd + t0,
+                                                                          ws.part + (size_t)(t0 / rpb) * kPartStride, 1, ws.gw,
+                                                                          none, loss_kind == MACR_LOSS_RUBIBCEBOTH ? 1 : 0)));
+    }
+    MACR_CHECK_LAUNCH("pair_fwd", st);
+    return MACR_OK;
+}
+
+/* macr_shard_backward_slice with the slice's per-block branch-vector rows at the blocks' indices in the whole batch, in a zeroed
+ * region (returned: (dev) fp32[ceil(B / (1024 / d))][2][d]); sum it over the ranks, then macr_shard_branch_fold_inv */
+extern "C" int macr_shard_backward_slice_inv(int loss_kind, int B, int d, int t0, int n, const float *rows3_slice, const float *w,
+                                             const float *wu, float *adam_pow, const macr_hyper *hp, float *losses,
+                                             float *stage_slice, void **branch_grads, size_t *branch_bytes, void *workspace,
+                                             size_t workspace_bytes, void *stream) {
+    MACR_REQUIRE(loss_kind == MACR_LOSS_RUBIBCEBOTH || loss_kind == MACR_LOSS_RUBIBCE, MACR_E_UNSUPPORTED,
+                 "shard_backward_slice_inv: loss_kind=%d", loss_kind);
+    MACR_REQUIRE(w && wu && adam_pow && losses && t0 >= 0 && n >= 0 && t0 + n <= B && (n == 0 || (rows3_slice && stage_slice)),
+                 MACR_E_INVALID, "shard_backward_slice_inv: bad argument");
+    MACR_REQUIRE(inv_slice_aligned(B, t0, n), MACR_E_INVALID, "shard_backward_slice_inv: slice [%d, %d) not cut at multiples of %d", t0, t0 + n, kInvAlign);
+    if (int e = validate_hyper(hp, "shard_backward_slice_inv")) return e;
+    MACR_REQUIRE(inv_split_serves(B, d), MACR_E_UNSUPPORTED, "shard_backward_slice_inv: B=%d needs more than 4096 blocks of %d positions", B, 1024 / d);
+    MACR_SHARD_COMMON_AS("shard_backward_slice_inv", true);
+    LossArgs L = loss_args(loss_kind, B, hp, losses);
+    L.part = ws.part; L.n_part = ws.nblk_pair; L.part2 = nullptr; L.n_part2 = 0;
+    L.lpart = ws.lpart; L.n_lpart = ws.nrb * ws.ncbx;
+    const float coef = hp->decay / (float)hp->batch_size_cfg;
+    const int lpr = d / 4, rpb = 256 / lpr, nblk = (n + rpb - 1) / rpb;                  // t0 / rpb + nblk <= ws.nblk_bwd = ws.nblk_pair
+    fill_words(ws.wblk, (size_t)ws.nblk_bwd * 2 * d, 0u, st);
+    // block k of the slice is block t0 / rpb + k of the whole batch and sums the same positions: its row goes THERE
+    // (a slice without triples still runs the last block: the step's lr_t, the beta powers and the losses)
+    MACR_DISPATCH_LPR(d, (k_pair_bwd_stage<LPR, false, false, true><<<nblk + 1, 256, 0, st>>>(
+                             n, ws.Bp, ws.nrb, ws.ncb, sw.iota, sw.iota + n, sw.iota + 2 * (size_t)n, rows3_slice,
+                             rows3_slice + (size_t)n * d, w, wu, ws.fwd + t0, ws.rowpart + t0, ws.colpart + t0, stage_slice,
+                             ws.wblk + (size_t)(t0 / rpb) * 2 * d, hp->alpha, hp->beta, coef, adam_pow, ws.scal, hp->lr, hp->beta1,
+                             hp->beta2, L, nullptr, B)));
+    MACR_CHECK_LAUNCH("pair_bwd", st);
+    if (branch_grads) *branch_grads = ws.wblk;
+    if (branch_bytes) *branch_bytes = (size_t)ws.nblk_bwd * 2 * d * 4;
+    return MACR_OK;
+}
+
+/* the complete set of block rows (the region of macr_shard_backward_slice_inv, summed over the ranks) folded in block order into
+ * the branch-vector partial rows macr_shard_apply_inv reads: the fold of macr_shard_backward_inv */
+extern "C" int macr_shard_branch_fold_inv(int B, int d, void *workspace, size_t workspace_bytes, void *stream) {
+    MACR_REQUIRE(inv_split_serves(B, d), MACR_E_UNSUPPORTED, "shard_branch_fold_inv: B=%d needs more than 4096 blocks of %d positions", B, 1024 / d);
+    MACR_SHARD_COMMON_AS("shard_branch_fold_inv", true);
+    k_branch_fold<<<(kBranchSlots * 2 * d + 255) / 256, 256, 0, st>>>(ws.nblk_bwd, 2 * d, ws.wblk, ws.gw);
+    MACR_CHECK_LAUNCH("branch_fold", st);
+    return MACR_OK;
+}
+
+extern "C" int macr_shard_apply_inv(int loss_kind, int B, int d, int n_users_loc, int n_items_loc, int u_lo, int u_stride, int i_lo,
+                                    int i_stride, const int32_t *u, const int32_t *i, const int32_t *j, float *P, float *Q, float *w,
+                                    float *wu, float *mP, float *vP, float *mQ, float *vQ, float *mw, float *vw, float *mwu,
+                                    float *vwu, float *gP, float *gQ, int32_t *touchedP, int32_t *touchedQ, const macr_hyper *hp,
+                                    const macr_lazy_adam *lazy, void *workspace, size_t workspace_bytes, void *stream) {
+    return shard_apply(loss_kind, B, d, n_users_loc, n_items_loc, u_lo, u_stride, i_lo, i_stride, u, i, j, P, Q, w, wu, mP, vP, mQ, vQ,
+                       mw, vw, mwu, vwu, gP, gQ, touchedP, touchedQ, hp, lazy, workspace, workspace_bytes, stream, true, true);
 }
 
 /* every row of the (local) tables brought to the current step: afterwards P, Q and the slots are what the per-step dense pass

@@ -249,14 +249,20 @@ class ShardedBPRMF(object):
     sharded = True
     _TRAIN = BPRMF._TRAIN
 
-    def __init__(self, args, data_config, device=None, seed=12345, layout="interleaved", deterministic=None):
+    def __init__(self, args, data_config, device=None, seed=12345, layout="interleaved", deterministic=None, invariant=None):
         """deterministic: the bit-reproducible sharded step (sharded_train.HipBackend(deterministic=True)).  None:
         MACR_SHARD_DETERMINISTIC=1 in the environment decides -- a switch of its own: its contract fixes the number of ranks, the
-        layout and the step form, which MACR_DETERMINISTIC's does not know."""
+        layout and the step form, which MACR_DETERMINISTIC's does not know.
+        invariant: the rank-count-invariant sharded step (HipBackend(invariant=True)): the same bits whatever the number of ranks,
+        the layout and the step form.  None: MACR_SHARD_INVARIANT=1 in the environment decides.  It keeps every promise of the
+        deterministic mode and wins where both are asked for."""
         from . import sharded_train, sharding
+        if invariant is None:
+            invariant = sharded_train.shard_invariant_from_env()
+        self.invariant = bool(invariant)
         if deterministic is None:
             deterministic = sharded_train.shard_deterministic_from_env()
-            if deterministic_from_env() and not deterministic:
+            if deterministic_from_env() and not deterministic and not self.invariant:
                 raise NotImplementedError("MACR_DETERMINISTIC=1 does not cover the row-sharded step (--row_shard 1): its "
                                           "bit-reproducible mode has a switch of its own, MACR_SHARD_DETERMINISTIC=1; set that, "
                                           "train unsharded or unset MACR_DETERMINISTIC")
@@ -299,7 +305,8 @@ class ShardedBPRMF(object):
                 raise NotImplementedError("a row-sharded model trains with one loss kind per run")
             P, Q, w, wu = self._init
             self._models[kind] = sharded_train.RowShardedMF(
-                None, None, w, wu, sharded_train.HipBackend(kind, self.d_pad, self._hyper, self.device, self.deterministic), rank=self.rank,
+                None, None, w, wu, sharded_train.HipBackend(kind, self.d_pad, self._hyper, self.device, self.deterministic, self.invariant),
+                rank=self.rank,
                 world=self.world, shards=(P, Q, self.n_users, self.n_items), layout=self._layout)
         return self._models[kind]
 
@@ -328,7 +335,8 @@ class ShardedBPRMF(object):
         m = self._model(kind)
         counts = None
         hb = getattr(batch, "_macr_host_batch", None)        # set by to_device_batch on THIS tensor object only
-        if hb is not None and hb.shape == tuple(batch.shape) and self.world > 1 and m.split and not ops.is_pair_loss(kind):
+        if hb is not None and hb.shape == tuple(batch.shape) and self.world > 1 and m.split and not ops.is_pair_loss(kind) \
+                and m._split_serves(hb.shape[1]):
             counts = m.route_counts_host(hb[0], hb[1], hb[2])
         out = m.step(batch[0], batch[1], batch[2], counts=counts)
         if losses is not None:

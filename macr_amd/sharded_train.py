@@ -24,7 +24,13 @@ entry points of include/macr_hip.h; the CPU tests plug the oracle in its place).
 Bit-reproducible mode (HipBackend(deterministic=True); MACR_SHARD_DETERMINISTIC=1 for the CLI): backward and apply run the
 macr_shard_*_det entry points (one owner per gradient row, branch-vector partial rows folded in block order), and the split
 step's two sums over the ranks whose operands overlap travel as one row per rank and are folded in rank order
-(RowShardedMF._all_reduce_folded), so that no result depends on the order a collective adds in.  Contract: include/macr_hip.h."""
+(RowShardedMF._all_reduce_folded), so that no result depends on the order a collective adds in.  Contract: include/macr_hip.h.
+
+Rank-count-invariant mode (HipBackend(invariant=True); MACR_SHARD_INVARIANT=1 for the CLI): the macr_shard_*_inv entry points.
+Gradient-row sums are cut at the run's start, the split step's slices at multiples of 32 positions (macr_shard_slice_inv), and
+the slices write loss partials and per-block branch-vector rows at the block's index in the whole batch: plain all-reduces
+(x + 0 + .. + 0), then every rank folds the complete set of block rows.  Losses, reassembled tables and slots, w, w_user and
+adam_pow are then the same bits for every number of ranks, layout, step form and lazy period (after a flush)."""
 import ctypes
 import os
 
@@ -38,6 +44,12 @@ def shard_deterministic_from_env():
     """MACR_SHARD_DETERMINISTIC=1 in the environment: the row-sharded step runs in its bit-reproducible mode (include/macr_hip.h,
     macr_shard_*_det).  A switch of its own, with its own contract: MACR_DETERMINISTIC covers the unsharded steps."""
     return os.environ.get("MACR_SHARD_DETERMINISTIC", "") == "1"
+
+
+def shard_invariant_from_env():
+    """MACR_SHARD_INVARIANT=1 in the environment: the row-sharded step runs in its rank-count-invariant mode (include/macr_hip.h,
+    macr_shard_*_inv).  A switch of its own; it implies what MACR_SHARD_DETERMINISTIC promises and wins if both are set."""
+    return os.environ.get("MACR_SHARD_INVARIANT", "") == "1"
 
 
 def row_range(n_rows, rank, world):
@@ -104,13 +116,17 @@ class HipBackend(object):
     """Device half on the MI355X: thin calls into libmacr_hip.so (no fallback)."""
     lazy_capable = True                 # the lazy dense Adam pass (include/macr_hip.h: macr_lazy_adam) exists on this backend
 
-    def __init__(self, kind, d, hyper, device, deterministic=False):
+    def __init__(self, kind, d, hyper, device, deterministic=False, invariant=False):
         """deterministic: the bit-reproducible step -- the workspace of macr_shard_workspace_bytes_det, backward / backward_slice /
         apply through the _det entry points; RowShardedMF takes the mode from here (and folds the split step's cross-rank sums
-        in rank order: fold_ranks)"""
+        in rank order: fold_ranks)
+        invariant: the rank-count-invariant step (wins over deterministic, whose promises it keeps) -- the _inv entry points, the
+        slices of macr_shard_slice_inv; RowShardedMF sums the split step's regions with plain all-reduces and folds the complete
+        set of block rows (branch_fold)"""
         from . import _lib, ops
         self._lib, self.ops, self.kind, self.d, self.hyper, self.device = _lib, ops, kind, d, hyper, device
-        self.deterministic = bool(deterministic)
+        self.invariant = bool(invariant)
+        self.deterministic = bool(deterministic) and not self.invariant
         self.ws, self.cap = None, 0
         self.adam_pow = torch.tensor([hyper.beta1, hyper.beta2], dtype=torch.float32, device=device)
         self.losses = torch.zeros(3, dtype=torch.float32, device=device)
@@ -118,7 +134,8 @@ class HipBackend(object):
     def _reserve(self, B):
         if B > self.cap:
             L = self._lib.lib()
-            n = (L.macr_shard_workspace_bytes_det if self.deterministic else L.macr_shard_workspace_bytes)(B, self.d)
+            n = (L.macr_shard_workspace_bytes_inv if self.invariant else L.macr_shard_workspace_bytes_det if self.deterministic
+                 else L.macr_shard_workspace_bytes)(B, self.d)
             if n == 0:
                 raise self._lib.MacrError(self._lib.E_UNSUPPORTED, "embed_size %d not in {32,64,128,256}" % self.d)
             self.ws, self.cap = torch.empty(n, dtype=torch.uint8, device=self.device), B
@@ -190,7 +207,7 @@ class HipBackend(object):
         o, L = self.ops, self._lib.lib()
         B = rows3.shape[1]
         ptr, nbytes = ctypes.c_void_p(), ctypes.c_size_t()
-        call = L.macr_shard_backward_det if self.deterministic else L.macr_shard_backward
+        call = L.macr_shard_backward_inv if self.invariant else L.macr_shard_backward_det if self.deterministic else L.macr_shard_backward
         self._lib.check(call(self.kind, B, self.d, o._ptr(rows3), o._ptr(shard.w), o._ptr(shard.wu),
                              o._ptr(self.adam_pow), ctypes.byref(self.hyper), o._ptr(self.losses),
                              ctypes.byref(ptr), ctypes.byref(nbytes), o._ptr(self.ws), self.ws.numel(), o._stream()))
@@ -222,16 +239,19 @@ class HipBackend(object):
 
     def slice_of(self, B, rank, world):
         t0, t1 = ctypes.c_int(), ctypes.c_int()
-        self._lib.check(self._lib.lib().macr_shard_slice(B, self.d, rank, world, ctypes.byref(t0), ctypes.byref(t1)))
+        L = self._lib.lib()
+        self._lib.check((L.macr_shard_slice_inv if self.invariant else L.macr_shard_slice)(B, self.d, rank, world, ctypes.byref(t0),
+                                                                                         ctypes.byref(t1)))
         return t0.value, t1.value
 
     def forward_slice(self, shard, B, t0, rows3_slice):
         self._reserve(B)
         o, L = self.ops, self._lib.lib()
         ptr, nbytes = ctypes.c_void_p(), ctypes.c_size_t()
-        self._lib.check(L.macr_shard_forward_slice(self.kind, B, self.d, t0, rows3_slice.shape[1], o._ptr(rows3_slice), o._ptr(shard.w),
-                                                   o._ptr(shard.wu), ctypes.byref(ptr), ctypes.byref(nbytes), o._ptr(self.ws),
-                                                   self.ws.numel(), o._stream()))
+        call = L.macr_shard_forward_slice_inv if self.invariant else L.macr_shard_forward_slice
+        self._lib.check(call(self.kind, B, self.d, t0, rows3_slice.shape[1], o._ptr(rows3_slice), o._ptr(shard.w),
+                             o._ptr(shard.wu), ctypes.byref(ptr), ctypes.byref(nbytes), o._ptr(self.ws),
+                             self.ws.numel(), o._stream()))
         return self._view(ptr, nbytes)                      # forward state + loss partials of the slice: sum over the ranks
 
     def bxb(self, B, rank, world):
@@ -246,11 +266,18 @@ class HipBackend(object):
         n = rows3_slice.shape[1]
         stage = torch.empty((3, n, self.d), dtype=torch.float32, device=self.device)
         ptr, nbytes = ctypes.c_void_p(), ctypes.c_size_t()
-        call = L.macr_shard_backward_slice_det if self.deterministic else L.macr_shard_backward_slice
+        call = (L.macr_shard_backward_slice_inv if self.invariant else L.macr_shard_backward_slice_det if self.deterministic
+                else L.macr_shard_backward_slice)
         self._lib.check(call(self.kind, B, self.d, t0, n, o._ptr(rows3_slice), o._ptr(shard.w), o._ptr(shard.wu),
                              o._ptr(self.adam_pow), ctypes.byref(self.hyper), o._ptr(self.losses), o._ptr(stage),
                              ctypes.byref(ptr), ctypes.byref(nbytes), o._ptr(self.ws), self.ws.numel(), o._stream()))
         return self.losses, stage, self._view(ptr, nbytes)
+
+    def branch_fold(self, B):
+        """invariant split step: the block-row region of backward_slice, summed over the ranks, folded in block order into the
+        branch-vector partial rows apply reads (macr_shard_branch_fold_inv)"""
+        o = self.ops
+        self._lib.check(self._lib.lib().macr_shard_branch_fold_inv(B, self.d, o._ptr(self.ws), self.ws.numel(), o._stream()))
 
     # ---- the deterministic split step's sum over the ranks of a workspace region that several ranks fill at the SAME indices:
     # the region goes into row `rank` of a zeroed (world, n) buffer (rank_rows), the caller all-reduces the buffer -- every
@@ -285,8 +312,9 @@ class HipBackend(object):
                 o._ptr(shard.gP), o._ptr(shard.gQ), o._ptr(shard.tP), o._ptr(shard.tQ), ctypes.byref(self.hyper))
         tail = (o._ptr(self.ws), self.ws.numel(), o._stream())
         lz = self._lazy(shard)
-        if self.deterministic:
-            self._lib.check(L.macr_shard_apply_det(*(head + (ctypes.byref(lz) if lz is not None else None,) + tail)))
+        if self.invariant or self.deterministic:
+            call = L.macr_shard_apply_inv if self.invariant else L.macr_shard_apply_det
+            self._lib.check(call(*(head + (ctypes.byref(lz) if lz is not None else None,) + tail)))
         elif lz is not None:
             self._lib.check(L.macr_shard_apply_lazy(*(head + (ctypes.byref(lz),) + tail)))
         else:
@@ -337,6 +365,7 @@ class RowShardedMF(object):
         self.tQ = torch.zeros(self._Q.shape[0], dtype=torch.int32, device=dev)
         self.backend = backend
         self.deterministic = bool(getattr(backend, "deterministic", False))     # (the mode is the backend's: it sized the workspace)
+        self.invariant = bool(getattr(backend, "invariant", False))
         # lazy dense Adam: row stamps + the library's step counter / lr_t ring; `_stale` = some row is behind the current step
         if lazy_period is None:
             env = os.environ.get("MACR_LAZY_ADAM", "")
@@ -479,6 +508,22 @@ class RowShardedMF(object):
             self.__dict__[key] = [self.backend.slice_of(B, r, self.world) for r in range(self.world)]
         return self.__dict__[key]
 
+    def _split_serves(self, B):
+        """the invariant split form needs one backward block per 1024 / d positions (include/macr_hip.h: macr_shard_slice_inv
+        refuses a batch beyond 4096 blocks); the replicated form serves such a batch -- with the same bits, by the contract"""
+        if not self.invariant:
+            return True
+        key = ("split_serves", B)
+        if key not in self.__dict__:
+            try:
+                self._slice_bounds(B)
+                self.__dict__[key] = True
+            except RuntimeError as e:
+                if getattr(e, "code", None) != -2:      # (_lib.E_UNSUPPORTED; anything else is an error)
+                    raise
+                self.__dict__[key] = False
+        return self.__dict__[key]
+
     def step_split(self, u, i, j, counts=None):
         """One step with forward and backward SPLIT over the ranks (branch losses): rank p handles the positions of its
         (B,B) row blocks.  Per rank and step: all-to-all of the 3B/W rows its slice needs (from their owners), an all-reduce of
@@ -486,6 +531,8 @@ class RowShardedMF(object):
         branch-vector gradient partials, all-to-all of the 3B/W gradient rows back to the owners, then the local Adam pass.
         Deterministic backend: the two all-reduces whose operands overlap (forward region, branch rows) carry one row per rank
         and are folded in rank order (_all_reduce_folded): W times their bytes on the wire, still latency-class messages.
+        Invariant backend: the slices' regions do not overlap -- plain all-reduces -- and the branch all-reduce carries the
+        complete block-row region (ceil(B / (1024 / d)) rows of 2 d floats instead of 8), which every rank then folds.
         counts: the (W, W) table of route() as python ints when the caller knows the batch on the host (no synchronisation)."""
         be, W, B = self.backend, self.world, u.numel()
         cnt, send_ref, recv_ref, rows = self.route(u, i, j)
@@ -536,6 +583,8 @@ class RowShardedMF(object):
             self._all_reduce_folded(branch, "branch")
         else:
             self._all_reduce(branch, "branch")
+        if self.invariant:                              # `branch` was the complete block-row region: its fold, on every rank
+            be.branch_fold(B)
         # 5. gradient rows back to the owners, into the staging rows macr_shard_apply reads
         back = torch.empty((n_send, d), dtype=self._P.dtype, device=self._P.device)
         self._all_to_all(back, stage.view(3 * n, d)[slot].contiguous(), send_counts, recv_counts, "grads_a2a")
@@ -551,7 +600,8 @@ class RowShardedMF(object):
         With several ranks and a branch loss the step is the SPLIT one (step_split; MACR_SHARD_SPLIT=0: the replicated
         forward / backward around one all-reduce of the batch's rows, below); `counts`: see step_split."""
         be = self.backend
-        if (self.world > 1 and self.split and hasattr(be, "slice_of") and not is_pair_loss(getattr(be, "kind", 1))):   # (per-pair: no (B,B) term)
+        if (self.world > 1 and self.split and hasattr(be, "slice_of") and not is_pair_loss(getattr(be, "kind", 1))   # (per-pair: no (B,B) term)
+                and self._split_serves(u.numel())):
             return self.step_split(u, i, j, counts)
         rows3 = be.gather(self, u, i, j)
         self._all_reduce(rows3, "rows")                           # 1. the batch's rows, everywhere

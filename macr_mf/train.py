@@ -216,6 +216,9 @@ def main(sweep=False):
     if args.row_shard != 1 and os.environ.get("MACR_SHARD_DETERMINISTIC", "") == "1":
         raise SystemExit("MACR_SHARD_DETERMINISTIC=1 is the bit-reproducible mode of the row-sharded step and this run is not "
                          "row-sharded: add --row_shard 1, or set MACR_DETERMINISTIC=1 for the unsharded step")
+    if args.row_shard != 1 and os.environ.get("MACR_SHARD_INVARIANT", "") == "1":
+        raise SystemExit("MACR_SHARD_INVARIANT=1 is the rank-count-invariant mode of the row-sharded step and this run is not "
+                         "row-sharded: add --row_shard 1, or set MACR_DETERMINISTIC=1 for the unsharded step")
     config = dict(n_users=data.n_users, n_items=data.n_items)
     if args.row_shard == 1:
         from macr_amd.mf import ShardedBPRMF
