@@ -21,32 +21,25 @@ Every shape is the smallest that reaches a place where an order could leak:
 2. collective-order independence: the same cases through Loopbacks whose all_reduce adds the ranks' tensors in reversed order,
    and in an order rotated by call count: bit-identical to the rank-order run (W >= 3, both step forms).
 3. accuracy: against oracle.mf_train_step / tests/bpr_ref.py at the tolerances of tests/test_gpu_shard_worlds.py.
-4. path and hygiene (asserted inside every deterministic run): the kernels of the last step; gradient scratch and row flags
+4. path and hygiene (asserted inside every deterministic run, tests/shard_rig.py): the kernels of the last step; gradient scratch and row flags
    clean after every step on every rank; the ranks of one run agree bit for bit on losses, w and w_user after every step.
 5. product: ShardedBPRMF under the variable, and two runs of the MF CLI with --row_shard 1: bit-identical checkpoints."""
-import functools
 import os
 import shutil
 import subprocess
 import sys
-import threading
 import types
 
 import numpy as np
 import pytest
 import torch
 
-import bpr_ref
-import oracle
 import shard_loopback
+import shard_rig
 from helpers import GOLD, REPO
+from shard_rig import ALL_FORMS, BOTH, BPR, ITEM, LR, NORMAL, SMALL, TABLES, ReversedLoopback, RotatingLoopback, bits, dev, set_form
 
 pytestmark = pytest.mark.gpu
-
-LR, DECAY, ALPHA, BETA, BS = 1e-3, 1e-5, 1e-2, 1e-3, 512
-BOTH, ITEM, NORMAL, BPR = "LOSS_RUBIBCEBOTH", "LOSS_RUBIBCE", "LOSS_NORMALBCE", "LOSS_BPR"
-TABLES = ("P", "Q", "mP", "vP", "mQ", "vQ")
-SMALL = ("mw", "vw", "mwu", "vwu")
 
 # name -> B, d, n_users, n_items, W, layout, lazy period, steps, flush after step, hot runs [(array, start, stop, row)]
 SHAPES = {
@@ -59,7 +52,6 @@ SHAPES = {
     "B777i": (777, 64, 901, 350, 3, "interleaved", 3, 7, 4, (("i", 0, 200, 0),)),
     "B777r": (777, 64, 901, 350, 3, "range", 3, 7, 4, (("i", 0, 200, 0),)),
 }
-ALL_FORMS = ((BOTH, True), (BOTH, False), (ITEM, True), (ITEM, False), (NORMAL, False), (BPR, False))
 CASES = ([("B300", k, s) for k, s in ALL_FORMS] + [("B100", k, s) for k, s in ALL_FORMS] + [("B257", k, s) for k, s in ALL_FORMS] +
          [(sh, BOTH, s) for sh in ("B4096W3", "B4096W16") for s in (True, False)] +
          [("B100d128", BOTH, True), ("B100d128", ITEM, True)] +
@@ -79,208 +71,23 @@ def ops():
     return _ops
 
 
-def dev(a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()       # (a writable copy: the problems' arrays are read-only)
-
-
-@functools.lru_cache(maxsize=None)
-def problem(B, d, n_users, n_items, steps, hot):
-    """tables, branch vectors and one batch per step: a fresh draw, the hot runs written over it, then spread over the batch's
-    blocks by a permutation"""
-    rs = np.random.RandomState(B + d + n_users)
-    P = (rs.standard_normal((n_users, d)) * 0.3).astype(np.float32)
-    Q = (rs.standard_normal((n_items, d)) * 0.3).astype(np.float32)
-    w, wu = (rs.standard_normal(d) * 0.3).astype(np.float32), (rs.standard_normal(d) * 0.3).astype(np.float32)
-    batches = []
-    for _ in range(steps):
-        b = dict(u=rs.choice(n_users, B, replace=B > n_users).astype(np.int32), i=rs.randint(0, n_items, B).astype(np.int32),
-                 j=rs.randint(0, n_items, B).astype(np.int32))
-        for name, lo, hi, row in hot:
-            b[name][lo:hi] = row
-        o = rs.permutation(B)
-        batches.append(tuple(b[k][o] for k in ("u", "i", "j")))
-    for a in (P, Q, w, wu) + tuple(x for b in batches for x in b):
-        a.setflags(write=False)
-    return P, Q, w, wu, tuple(batches)
+def spec_of(shape):
+    """(problem, case without its kind and form) of a shape, as shard_rig.run_world takes them"""
+    B, d, n_users, n_items, W, layout, lazy, steps, flush_after, hot = SHAPES[shape]
+    return (B, d, n_users, n_items, steps, flush_after, hot), (W, layout, lazy)
 
 
 def problem_of(shape):
-    B, d, n_users, n_items, W, layout, lazy, steps, flush_after, hot = SHAPES[shape]
-    return problem(B, d, n_users, n_items, steps, hot)
-
-
-@functools.lru_cache(maxsize=None)
-def reference(B, d, n_users, n_items, steps, hot, kind_name):
-    """the single-process CPU run of a problem, once: losses per step, m of P and Q after the first step, final P, Q, w, w_user"""
-    P, Q, w, wu, batches = problem(B, d, n_users, n_items, steps, hot)
-    if kind_name == BPR:
-        ref = bpr_ref.Adam([P, Q], LR)
-        losses, m1 = [], None
-        for u, i, j in batches:
-            loss, mf, reg, dP, dQ = bpr_ref.mf_bpr(ref.params[0], ref.params[1], u, i, j, DECAY, BS)
-            ref.step([dP, dQ])
-            losses.append(np.asarray([loss, mf, reg]))
-            m1 = m1 or (ref.m[0].copy(), ref.m[1].copy())
-        return losses, m1, ref.params[0], ref.params[1], w, wu
-    Po, Qo, wo, wuo = P.copy(), Q.copy(), w.copy(), wu.copy()
-    st = oracle.AdamState([P.shape, Q.shape, (d,), (d,)])
-    losses, m1 = [], None
-    for u, i, j in batches:
-        losses.append(oracle.mf_train_step(getattr(oracle, kind_name), u, i, j, Po, Qo, wo, wuo, st, LR, DECAY, ALPHA, BETA,
-                                           BS).copy())
-        m1 = m1 or (st.m[0].copy(), st.m[1].copy())
-    return losses, m1, Po, Qo, wo, wuo
-
-
-# ----------------------------------------------------------------------------- collectives that add in another order
-class OrderedLoopback(shard_loopback.Loopback):
-    """Loopback whose all_reduce adds the ranks' tensors in the order `order(call)` gives (broadcast and all_to_all add nothing)"""
-
-    def __init__(self, world, timeout=120.0):
-        super(OrderedLoopback, self).__init__(world, timeout)
-        self.calls = 0
-
-    def order(self, call):
-        raise NotImplementedError
-
-    def all_reduce(self, rank, t):
-        self.slots[rank] = t
-        if self.barrier.wait() == 0:                      # exactly one thread sums
-            order = self.order(self.calls)
-            self.calls += 1
-            assert sorted(order) == list(range(self.world))
-            acc = self.slots[order[0]].clone()
-            for r in order[1:]:
-                acc += self.slots[r]
-            self.result = acc
-        self.barrier.wait()
-        t.copy_(self.result)
-        self.barrier.wait()
-
-
-class ReversedLoopback(OrderedLoopback):
-    def order(self, call):
-        return list(range(self.world - 1, -1, -1))
-
-
-class RotatingLoopback(OrderedLoopback):
-    def order(self, call):
-        k = (call + 1) % self.world                       # (never the identity twice in a row; the first call starts at rank 1)
-        return list(range(k, self.world)) + list(range(k))
-
-
-_LAUNCH = threading.Lock()
-
-
-def serial_backend(sharded_train):
-    """HipBackend whose library calls are taken one rank at a time: the kernel timing marks of the library are one list per
-    process, and W threads launch into it"""
-    class SerialBackend(sharded_train.HipBackend):
-        pass
-
-    def locked(fn):
-        @functools.wraps(fn)
-        def call(self, *a, **kw):
-            with _LAUNCH:
-                return fn(self, *a, **kw)
-        return call
-    for name in ("gather", "lazy_rows", "lazy_flush", "forward_and_bxb", "backward", "route", "forward_slice", "bxb", "backward_slice",
-                 "stage_rows", "apply", "rank_rows", "fold_ranks"):
-        setattr(SerialBackend, name, locked(getattr(sharded_train.HipBackend, name)))
-
-    return SerialBackend
+    B, d, n_users, n_items, steps, flush_after, hot = spec_of(shape)[0]
+    return shard_rig.problem(B, d, n_users, n_items, steps, hot)
 
 
 def run_world(ops, case, deterministic, loopback=None):
-    """the case's steps on its W ranks -> per rank: what it saw after every step and its shard at the end (numpy)"""
-    from macr_amd import sharded_train
+    """the case's steps on its W ranks -> per rank: what it saw after every step and its shard at the end (numpy); the
+    deterministic runs assert their path and hygiene inside (shard_rig.run_world)"""
     shape, kind_name, split = case
-    B, d, n_users, n_items, W, layout, lazy, steps, flush_after, hot = SHAPES[shape]
-    P, Q, w, wu, batches = problem_of(shape)
-    kind, device = getattr(ops, kind_name), torch.device("cuda")
-    pair = kind_name in (NORMAL, BPR)
-    Backend = serial_backend(sharded_train)
-
-    def rank_main(rank, comm):
-        hyper = ops.make_hyper(LR, DECAY, ALPHA, BETA, BS)
-        backend = Backend(kind, d, hyper, device, deterministic=deterministic)
-        model = shard_loopback.LoopbackMF(comm, rank, dev(P), dev(Q), dev(w), dev(wu), backend, layout=layout, lazy_period=lazy)
-        assert model.deterministic == deterministic and backend.deterministic == deterministic
-        assert model.split == split and model.lazy_period == lazy
-        if deterministic:
-            L = backend._lib.lib()
-            assert L.macr_shard_workspace_bytes_det(B, d) > L.macr_shard_workspace_bytes(B, d)
-        out = dict(losses=[], w=[], wu=[], own_u=model.own_u, own_i=model.own_i)
-        for k, (u, i, j) in enumerate(batches):
-            last = k == len(batches) - 1
-            if last:                                    # one rank opens the timing, every rank's launches of the step go on its list
-                if W > 1:
-                    comm.barrier.wait()
-                if rank == 0:
-                    ops.timing_begin()
-                if W > 1:
-                    comm.barrier.wait()
-            out["losses"].append(model.step(dev(u), dev(i), dev(j)).cpu().numpy().copy())
-            if last:
-                if W > 1:
-                    comm.barrier.wait()
-                if rank == 0:
-                    out["kernels"] = {n for n, _ in ops.timing_end(250)}
-                if W > 1:
-                    comm.barrier.wait()
-            out["w"].append(model.w.cpu().numpy())
-            out["wu"].append(model.wu.cpu().numpy())
-            if deterministic:                           # the gradient scratch and the row flags are left clean by every step
-                assert not bool(model.gP.any()) and not bool(model.gQ.any()), "step %d: gradient scratch not zero" % k
-                assert int(model.tP.sum()) == 0 and int(model.tQ.sum()) == 0, "step %d: row flags left set" % k
-                assert backend.ws.numel() == backend._lib.lib().macr_shard_workspace_bytes_det(B, d)
-            if k == 0:
-                out["m1P"], out["m1Q"] = model._mP.cpu(), model._mQ.cpu()
-            if flush_after is not None and k + 1 == flush_after:
-                model.flush()                           # (an evaluation, a checkpoint: every row brought to the current step)
-        for name in TABLES:
-            out[name] = getattr(model, name).cpu()      # (flushes what the lazy pass left behind)
-        for name in SMALL:
-            out[name] = getattr(model, name).cpu()
-        out["adam_pow"] = backend.adam_pow.cpu()
-        if lazy > 1:
-            out["stP"], out["stQ"] = model.stP.cpu(), model.stQ.cpu()      # the row stamps after a flush
-        return out
-
-    if loopback is None:
-        ranks = shard_loopback.run_ranks(W, rank_main, timeout=120.0)
-    else:
-        saved = shard_loopback.Loopback
-        shard_loopback.Loopback = loopback              # (run_ranks builds its Loopback by this name)
-        try:
-            ranks = shard_loopback.run_ranks(W, rank_main, timeout=120.0)
-        finally:
-            shard_loopback.Loopback = saved
-    if deterministic:
-        check_path_and_hygiene(case, ranks)
-    return ranks
-
-
-def check_path_and_hygiene(case, ranks):
-    shape, kind_name, split = case
-    lazy, steps = SHAPES[shape][6], SHAPES[shape][7]
-    pair = kind_name in (NORMAL, BPR)
-    kernels = ranks[0]["kernels"]
-    assert "seg_reduce" in kernels and "seg_fold" in kernels, kernels
-    assert ("branch_fold" in kernels) == (not pair), kernels
-    assert not kernels & {"seg_index", "seg_sum", "adam_indexed"}, kernels
-    assert ("adam_lazy" in kernels) == (lazy > 1) and ("adam_dense" in kernels) == (lazy == 1), kernels
-    assert ("fold_ranks" in kernels) == split, kernels
-    for r in ranks[1:]:                                 # the ranks of one run agree bit for bit after every step
-        for k in range(steps):
-            assert bits(r["losses"][k], ranks[0]["losses"][k]), "step %d: losses differ across ranks" % k
-            assert bits(r["w"][k], ranks[0]["w"][k]) and bits(r["wu"][k], ranks[0]["wu"][k]), "step %d: w / w_user differ across ranks" % k
-
-
-def bits(a, b):
-    """same shape, same bits"""
-    a, b = (x.numpy() if torch.is_tensor(x) else np.asarray(x) for x in (a, b))
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+    spec, where = spec_of(shape)
+    return shard_rig.run_world(ops, spec, (kind_name, split) + where, "det" if deterministic else "plain", loopback)["ranks"]
 
 
 def differences(x, y):
@@ -303,12 +110,6 @@ def first_run(ops, case):
     if case not in _first:
         _first[case] = run_world(ops, case, True)
     return _first[case]
-
-
-def set_form(monkeypatch, split):
-    monkeypatch.setenv("MACR_SHARD_SPLIT", "1" if split else "0")
-    for name in ("MACR_SHARD_ROUTE_TORCH", "MACR_SEG_UNFUSED", "MACR_LAZY_ADAM"):
-        monkeypatch.delenv(name, raising=False)
 
 
 # ----------------------------------------------------------------------------- 1. repeatability
@@ -348,7 +149,7 @@ def test_against_the_cpu_restatements(ops, monkeypatch, record_property, case):
     shape, kind_name, split = case
     B, d, n_users, n_items, W, layout, lazy, steps, flush_after, hot = SHAPES[shape]
     ranks = first_run(ops, case)
-    want_losses, want_m1, Po, Qo, wo, wuo = reference(B, d, n_users, n_items, steps, hot, kind_name)
+    want_losses, want_m1, Po, Qo, wo, wuo = shard_rig.cpu_reference(B, d, n_users, n_items, steps, hot, kind_name)
     full = {}
     for name in ("P", "m1P"):
         full[name] = shard_loopback.reassemble([r[name] for r in ranks], [r["own_u"] for r in ranks], n_users).numpy()

@@ -25,29 +25,22 @@ dense pass).
    clean after every step on every rank.
 5. on record, not asserted: whether MACR_SHARD_DETERMINISTIC worlds differed from their own world 1 on the same problems.
 6. product: ShardedBPRMF under the variable; the MF CLI as one process and as two ranks: identical losses and checkpoints."""
-import functools
 import os
 import shutil
 import subprocess
 import sys
-import threading
 import types
 
 import numpy as np
 import pytest
 import torch
 
-import bpr_ref
-import oracle
-import shard_loopback
+import shard_rig
 from helpers import GOLD, REPO
+from shard_rig import (ALL_FORMS, BOTH, ITEM, LR, DECAY, ALPHA, BETA, BS, SMALL, TABLES, ReversedLoopback, RotatingLoopback, bits,
+                       set_form)
 
 pytestmark = pytest.mark.gpu
-
-LR, DECAY, ALPHA, BETA, BS = 1e-3, 1e-5, 1e-2, 1e-3, 512
-BOTH, ITEM, NORMAL, BPR = "LOSS_RUBIBCEBOTH", "LOSS_RUBIBCE", "LOSS_NORMALBCE", "LOSS_BPR"
-TABLES = ("P", "Q", "mP", "vP", "mQ", "vQ")
-SMALL = ("mw", "vw", "mwu", "vwu")
 
 # name -> B, d, n_users, n_items, steps, flush after step, hot runs [(array, start, stop, row)]
 PROBLEMS = {
@@ -59,7 +52,6 @@ PROBLEMS = {
     "P777": (777, 64, 901, 350, 7, 4, (("i", 0, 200, 0),)),
     "P16416": (16416, 256, 300, 80, 2, None, (("i", 0, 130, 0),)),      # 4104 backward blocks: beyond the split form's 4096
 }
-ALL_FORMS = ((BOTH, True), (BOTH, False), (ITEM, True), (ITEM, False), (NORMAL, False), (BPR, False))
 # a case: (problem, kind, split, W, layout, lazy period)
 CASES = ([("P300", k, s, W, lay, 1) for k, s in ALL_FORMS for W in (2, 3, 5) for lay in ("range", "interleaved")] +
          [("P100", k, s, W, "interleaved", 1) for k, s in ALL_FORMS for W in (3, 8, 16)] +
@@ -67,8 +59,6 @@ CASES = ([("P300", k, s, W, lay, 1) for k, s in ALL_FORMS for W in (2, 3, 5) for
          [("P4096", BOTH, s, W, "interleaved", 1) for s in (True, False) for W in (3, 16)] +
          [("P100d", BOTH, True, 8, "interleaved", 1), ("P100d", ITEM, True, 8, "interleaved", 1)] +
          [("P777", BOTH, s, 3, lay, K) for s in (True, False) for lay in ("range", "interleaved") for K in (2, 3)])
-# the modes a world can run in -> HipBackend keywords
-MODES = {"inv": dict(invariant=True), "det": dict(deterministic=True), "plain": {}}
 
 
 def case_id(c):
@@ -88,193 +78,21 @@ def ops():
     return _ops
 
 
-def dev(a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()       # (a writable copy: the problems' arrays are read-only)
-
-
-@functools.lru_cache(maxsize=None)
 def problem(name):
-    """tables, branch vectors and one batch per step: a fresh draw, the hot runs written over it, then spread over the batch's
-    blocks by a permutation"""
     B, d, n_users, n_items, steps, flush_after, hot = PROBLEMS[name]
-    rs = np.random.RandomState(B + d + n_users)
-    P = (rs.standard_normal((n_users, d)) * 0.3).astype(np.float32)
-    Q = (rs.standard_normal((n_items, d)) * 0.3).astype(np.float32)
-    w, wu = (rs.standard_normal(d) * 0.3).astype(np.float32), (rs.standard_normal(d) * 0.3).astype(np.float32)
-    batches = []
-    for _ in range(steps):
-        b = dict(u=rs.choice(n_users, B, replace=B > n_users).astype(np.int32), i=rs.randint(0, n_items, B).astype(np.int32),
-                 j=rs.randint(0, n_items, B).astype(np.int32))
-        for arr, lo, hi, row in hot:
-            b[arr][lo:hi] = row
-        o = rs.permutation(B)
-        batches.append(tuple(b[k][o] for k in ("u", "i", "j")))
-    for a in (P, Q, w, wu) + tuple(x for b in batches for x in b):
-        a.setflags(write=False)
-    return P, Q, w, wu, tuple(batches)
+    return shard_rig.problem(B, d, n_users, n_items, steps, hot)
 
 
-@functools.lru_cache(maxsize=None)
 def cpu_reference(name, kind_name):
-    """the single-process CPU run of a problem, once: losses per step, m of P and Q after the first step, final P, Q, w, w_user"""
     B, d, n_users, n_items, steps, flush_after, hot = PROBLEMS[name]
-    P, Q, w, wu, batches = problem(name)
-    if kind_name == BPR:
-        ref = bpr_ref.Adam([P, Q], LR)
-        losses, m1 = [], None
-        for u, i, j in batches:
-            loss, mf, reg, dP, dQ = bpr_ref.mf_bpr(ref.params[0], ref.params[1], u, i, j, DECAY, BS)
-            ref.step([dP, dQ])
-            losses.append(np.asarray([loss, mf, reg]))
-            m1 = m1 or (ref.m[0].copy(), ref.m[1].copy())
-        return losses, m1, ref.params[0], ref.params[1], w, wu
-    Po, Qo, wo, wuo = P.copy(), Q.copy(), w.copy(), wu.copy()
-    st = oracle.AdamState([P.shape, Q.shape, (d,), (d,)])
-    losses, m1 = [], None
-    for u, i, j in batches:
-        losses.append(oracle.mf_train_step(getattr(oracle, kind_name), u, i, j, Po, Qo, wo, wuo, st, LR, DECAY, ALPHA, BETA,
-                                           BS).copy())
-        m1 = m1 or (st.m[0].copy(), st.m[1].copy())
-    return losses, m1, Po, Qo, wo, wuo
-
-
-# ----------------------------------------------------------------------------- collectives that add in another order
-class OrderedLoopback(shard_loopback.Loopback):
-    """Loopback whose all_reduce adds the ranks' tensors in the order `order(call)` gives (broadcast and all_to_all add nothing)"""
-
-    def __init__(self, world, timeout=120.0):
-        super(OrderedLoopback, self).__init__(world, timeout)
-        self.calls = 0
-
-    def order(self, call):
-        raise NotImplementedError
-
-    def all_reduce(self, rank, t):
-        self.slots[rank] = t
-        if self.barrier.wait() == 0:                      # exactly one thread sums
-            order = self.order(self.calls)
-            self.calls += 1
-            assert sorted(order) == list(range(self.world))
-            acc = self.slots[order[0]].clone()
-            for r in order[1:]:
-                acc += self.slots[r]
-            self.result = acc
-        self.barrier.wait()
-        t.copy_(self.result)
-        self.barrier.wait()
-
-
-class ReversedLoopback(OrderedLoopback):
-    def order(self, call):
-        return list(range(self.world - 1, -1, -1))
-
-
-class RotatingLoopback(OrderedLoopback):
-    def order(self, call):
-        k = (call + 1) % self.world                       # (never the identity twice in a row; the first call starts at rank 1)
-        return list(range(k, self.world)) + list(range(k))
-
-
-_LAUNCH = threading.Lock()
-
-
-def serial_backend(sharded_train):
-    """HipBackend whose library calls are taken one rank at a time: the kernel timing marks of the library are one list per
-    process, and W threads launch into it"""
-    class SerialBackend(sharded_train.HipBackend):
-        pass
-
-    def locked(fn):
-        @functools.wraps(fn)
-        def call(self, *a, **kw):
-            with _LAUNCH:
-                return fn(self, *a, **kw)
-        return call
-    for name in ("gather", "lazy_rows", "lazy_flush", "forward_and_bxb", "backward", "route", "forward_slice", "bxb", "backward_slice",
-                 "stage_rows", "apply", "rank_rows", "fold_ranks", "branch_fold"):
-        setattr(SerialBackend, name, locked(getattr(sharded_train.HipBackend, name)))
-    return SerialBackend
+    return shard_rig.cpu_reference(B, d, n_users, n_items, steps, hot, kind_name)
 
 
 def run_world(ops, case, mode="inv", loopback=None):
     """the case's steps on its W ranks -> what the contract speaks of: losses, w, w_user after every step per rank; the
-    reassembled tables and slots after every flush; the branch slots and adam_pow at the end"""
-    from macr_amd import sharded_train
-    name, kind_name, split, W, layout, lazy = case
-    B, d, n_users, n_items, steps, flush_after, hot = PROBLEMS[name]
-    P, Q, w, wu, batches = problem(name)
-    kind, device = getattr(ops, kind_name), torch.device("cuda")
-    pair = kind_name in (NORMAL, BPR)
-    Backend = serial_backend(sharded_train)
-
-    def tables_of(model):
-        return {t: getattr(model, t).cpu() for t in TABLES}          # (the properties flush what the lazy pass left behind)
-
-    def rank_main(rank, comm):
-        hyper = ops.make_hyper(LR, DECAY, ALPHA, BETA, BS)
-        backend = Backend(kind, d, hyper, device, **MODES[mode])
-        model = shard_loopback.LoopbackMF(comm, rank, dev(P), dev(Q), dev(w), dev(wu), backend, layout=layout, lazy_period=lazy)
-        assert model.invariant == (mode == "inv") == backend.invariant and model.deterministic == (mode == "det")
-        assert model.split == split and model.lazy_period == lazy
-        out = dict(losses=[], w=[], wu=[], own_u=model.own_u, own_i=model.own_i, flushed=[])
-        for k, (u, i, j) in enumerate(batches):
-            last = k == len(batches) - 1
-            if last:                                    # one rank opens the timing, every rank's launches of the step go on its list
-                comm.barrier.wait()
-                if rank == 0:
-                    ops.timing_begin()
-                comm.barrier.wait()
-            out["losses"].append(model.step(dev(u), dev(i), dev(j)).cpu().numpy().copy())
-            if last:
-                comm.barrier.wait()
-                if rank == 0:
-                    out["kernels"] = {n for n, _ in ops.timing_end(250)}
-                comm.barrier.wait()
-            out["w"].append(model.w.cpu().numpy())
-            out["wu"].append(model.wu.cpu().numpy())
-            if mode == "inv":                           # the gradient scratch and the row flags are left clean by every step
-                assert not bool(model.gP.any()) and not bool(model.gQ.any()), "step %d: gradient scratch not zero" % k
-                assert int(model.tP.sum()) == 0 and int(model.tQ.sum()) == 0, "step %d: row flags left set" % k
-                assert backend.ws.numel() == backend._lib.lib().macr_shard_workspace_bytes_inv(B, d)
-            if k == 0:
-                out["m1P"], out["m1Q"] = model._mP.cpu(), model._mQ.cpu()
-            if flush_after is not None and k + 1 == flush_after:
-                out["flushed"].append(tables_of(model))  # (an evaluation, a checkpoint: every row brought to the current step)
-        out["flushed"].append(tables_of(model))
-        for s in SMALL:
-            out[s] = getattr(model, s).cpu()
-        out["adam_pow"] = backend.adam_pow.cpu()
-        return out
-
-    saved = shard_loopback.Loopback
-    if loopback is not None:
-        shard_loopback.Loopback = loopback              # (run_ranks builds its Loopback by this name)
-    try:
-        ranks = shard_loopback.run_ranks(W, rank_main, timeout=120.0)
-    finally:
-        shard_loopback.Loopback = saved
-    # ---- what the contract compares: reassembled tables, and what every rank must hold alike
-    own_u, own_i = [r["own_u"] for r in ranks], [r["own_i"] for r in ranks]
-    full = []
-    for f in range(len(ranks[0]["flushed"])):
-        full.append({t: shard_loopback.reassemble([r["flushed"][f][t] for r in ranks], own_u if t.endswith("P") else own_i,
-                                                  n_users if t.endswith("P") else n_items) for t in TABLES})
-    world = dict(ranks=ranks, full=full,
-                 m1P=shard_loopback.reassemble([r["m1P"] for r in ranks], own_u, n_users),
-                 m1Q=shard_loopback.reassemble([r["m1Q"] for r in ranks], own_i, n_items))
-    if mode == "inv":
-        kernels = ranks[0]["kernels"]
-        assert "seg_reduce_inv" in kernels and "seg_fold_inv" in kernels, kernels
-        assert not kernels & {"seg_reduce", "seg_fold", "seg_index", "seg_sum", "adam_indexed", "fold_ranks"}, kernels
-        assert ("branch_fold" in kernels) == (not pair), kernels
-        assert ("adam_lazy" in kernels) == (lazy > 1) and ("adam_dense" in kernels) == (lazy == 1), kernels
-    return world
-
-
-def bits(a, b):
-    """same shape, same bits"""
-    a, b = (x.numpy() if torch.is_tensor(x) else np.asarray(x) for x in (a, b))
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+    reassembled tables and slots after every flush; the branch slots and adam_pow at the end (shard_rig.run_world, which asserts
+    the mode's path and hygiene inside)"""
+    return shard_rig.run_world(ops, PROBLEMS[case[0]], case[1:], mode, loopback)
 
 
 def differences(x, ref):
@@ -299,12 +117,6 @@ def first_run(ops, case, mode="inv"):
     if (case, mode) not in _first:
         _first[(case, mode)] = run_world(ops, case, mode)
     return _first[(case, mode)]
-
-
-def set_form(monkeypatch, split):
-    monkeypatch.setenv("MACR_SHARD_SPLIT", "1" if split else "0")
-    for name in ("MACR_SHARD_ROUTE_TORCH", "MACR_SEG_UNFUSED", "MACR_LAZY_ADAM", "MACR_SHARD_INVARIANT", "MACR_SHARD_DETERMINISTIC"):
-        monkeypatch.delenv(name, raising=False)
 
 
 def world_one(ops, monkeypatch, case, mode="inv"):

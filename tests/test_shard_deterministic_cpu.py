@@ -2,18 +2,21 @@
 entry points across the header, the ctypes table and the library's exports; the workspace size function; what the _det calls
 refuse, next to their plain counterparts; the environment switch.  Argument validation comes before any device work, so the
 pointers handed in are never dereferenced (as in tests/test_deterministic_cpu.py)."""
-import ctypes
+import functools
 import os
 import re
 import types
 
 import pytest
 
+import shard_calls
 from helpers import REPO
+from shard_calls import B, D, _hyper, aligned_mem, apply, backward
+
+backward_slice = functools.partial(shard_calls.backward_slice, t0=10, n=50)      # (a slice that begins at no block boundary)
 
 NEW = ("macr_shard_workspace_bytes_det", "macr_shard_backward_det", "macr_shard_backward_slice_det", "macr_shard_apply_det",
        "macr_shard_fold_ranks")
-B, D = 300, 64
 
 
 @pytest.fixture(scope="module")
@@ -26,45 +29,7 @@ def lib():
 
 @pytest.fixture(scope="module")
 def mem():
-    """a 256-byte aligned host address standing in for every buffer"""
-    buf = ctypes.create_string_buffer(8192)
-    return buf, ctypes.c_void_p((ctypes.addressof(buf) + 255) & ~255)
-
-
-def _hyper(lib, **over):
-    a = dict(lr=1e-3, beta1=0.9, beta2=0.999, adam_eps=1e-8, decay=1e-5, alpha=1e-2, beta=1e-3, batch_size_cfg=1024)
-    a.update(over)
-    return lib.Hyper(*[a[n] for n, _ in lib.Hyper._fields_])
-
-
-def backward(lib, mem, det, kind=None, ws_bytes=1 << 30, rows3="p", hp=None):
-    p, L = mem[1], lib.lib()
-    hp = hp or _hyper(lib)
-    call = L.macr_shard_backward_det if det else L.macr_shard_backward
-    return call(lib.LOSS_RUBIBCEBOTH if kind is None else kind, B, D, p if rows3 == "p" else None, p, p, p, ctypes.byref(hp), p,
-                None, None, p, ws_bytes, None)
-
-
-def backward_slice(lib, mem, det, kind=None, ws_bytes=1 << 30, t0=10, n=50, w="p"):
-    p, L = mem[1], lib.lib()
-    hp = _hyper(lib)
-    call = L.macr_shard_backward_slice_det if det else L.macr_shard_backward_slice
-    return call(lib.LOSS_RUBIBCEBOTH if kind is None else kind, B, D, t0, n, p, p if w == "p" else None, p, p, ctypes.byref(hp), p, p,
-                None, None, p, ws_bytes, None)
-
-
-def apply(lib, mem, form, ws_bytes=1 << 30, u="p", lazy_period=4, n_users_loc=40):
-    """form: "plain" (macr_shard_apply), "lazy" (macr_shard_apply_lazy), "det" (lazy = NULL), "det_lazy" """
-    p, L = mem[1], lib.lib()
-    hp = _hyper(lib)
-    lz = lib.LazyAdam(p, p, p, lazy_period)
-    head = [lib.LOSS_RUBIBCEBOTH, B, D, n_users_loc, 50, 0, 1, 0, 1, p if u == "p" else None, p, p] + [p] * 16 + [ctypes.byref(hp)]
-    tail = [p, ws_bytes, None]
-    if form == "plain":
-        return L.macr_shard_apply(*(head + tail))
-    if form == "lazy":
-        return L.macr_shard_apply_lazy(*(head + [ctypes.byref(lz)] + tail))
-    return L.macr_shard_apply_det(*(head + [ctypes.byref(lz) if form == "det_lazy" else None] + tail))
+    return aligned_mem()
 
 
 # ----------------------------------------------------------------------------- the C ABI
@@ -111,10 +76,10 @@ def test_workspace_size_is_zero_for_an_unsupported_width(lib):
 def test_backward_det_refuses_what_backward_refuses(lib, mem):
     for over in (dict(kind=lib.LOSS_RUBIBPR), dict(kind=lib.LOSS_RUBIBCE_EGO), dict(kind=77), dict(rows3=None),
                  dict(hp=_hyper(lib, batch_size_cfg=0)), dict(hp=_hyper(lib, beta1=1.5))):
-        plain = backward(lib, mem, False, **over)
+        plain = backward(lib, mem, "plain", **over)
         assert plain == lib.E_INVALID, over
-        assert backward(lib, mem, True, **over) == plain, over
-    assert backward(lib, mem, False, ws_bytes=16) == lib.E_WORKSPACE == backward(lib, mem, True, ws_bytes=16)
+        assert backward(lib, mem, "det", **over) == plain, over
+    assert backward(lib, mem, "plain", ws_bytes=16) == lib.E_WORKSPACE == backward(lib, mem, "det", ws_bytes=16)
     assert b"workspace" in lib.lib().macr_last_error()
 
 
@@ -122,9 +87,9 @@ def test_backward_slice_det_refuses_what_backward_slice_refuses(lib, mem):
     for over, code in ((dict(kind=lib.LOSS_NORMALBCE), lib.E_UNSUPPORTED), (dict(kind=lib.LOSS_BPR), lib.E_UNSUPPORTED),
                        (dict(kind=lib.LOSS_RUBIBPR), lib.E_UNSUPPORTED), (dict(w=None), lib.E_INVALID),
                        (dict(t0=280, n=50), lib.E_INVALID), (dict(t0=-1), lib.E_INVALID), (dict(ws_bytes=16), lib.E_WORKSPACE)):
-        plain = backward_slice(lib, mem, False, **over)
+        plain = backward_slice(lib, mem, "plain", **over)
         assert plain == code, over
-        assert backward_slice(lib, mem, True, **over) == plain, over
+        assert backward_slice(lib, mem, "det", **over) == plain, over
 
 
 def test_apply_det_refuses_what_apply_refuses(lib, mem):
@@ -141,9 +106,9 @@ def test_det_calls_refuse_a_workspace_of_the_plain_size(lib, mem):
     plain, det = L.macr_shard_workspace_bytes(B, D), L.macr_shard_workspace_bytes_det(B, D)
     assert det > plain
     # (the plain calls reach their launches with this size: not called here, there is no device)
-    for rc in (backward(lib, mem, True, ws_bytes=plain), backward(lib, mem, True, kind=lib.LOSS_NORMALBCE, ws_bytes=plain),
-               backward_slice(lib, mem, True, ws_bytes=plain), apply(lib, mem, "det", ws_bytes=plain),
-               apply(lib, mem, "det_lazy", ws_bytes=plain), backward(lib, mem, True, ws_bytes=det - 1)):
+    for rc in (backward(lib, mem, "det", ws_bytes=plain), backward(lib, mem, "det", kind=lib.LOSS_NORMALBCE, ws_bytes=plain),
+               backward_slice(lib, mem, "det", ws_bytes=plain), apply(lib, mem, "det", ws_bytes=plain),
+               apply(lib, mem, "det_lazy", ws_bytes=plain), backward(lib, mem, "det", ws_bytes=det - 1)):
         assert rc == lib.E_WORKSPACE
         assert b"workspace" in L.macr_last_error()
 

@@ -12,10 +12,10 @@ import types
 import pytest
 
 from helpers import REPO
+from shard_calls import B, D, _hyper, aligned_mem, apply, backward, backward_slice, forward_slice
 
 NEW = ("macr_shard_workspace_bytes_inv", "macr_shard_slice_inv", "macr_shard_backward_inv", "macr_shard_forward_slice_inv",
        "macr_shard_backward_slice_inv", "macr_shard_branch_fold_inv", "macr_shard_apply_inv")
-B, D = 300, 64
 ALIGN = 32
 
 
@@ -29,51 +29,7 @@ def lib():
 
 @pytest.fixture(scope="module")
 def mem():
-    """a 256-byte aligned host address standing in for every buffer"""
-    buf = ctypes.create_string_buffer(8192)
-    return buf, ctypes.c_void_p((ctypes.addressof(buf) + 255) & ~255)
-
-
-def _hyper(lib, **over):
-    a = dict(lr=1e-3, beta1=0.9, beta2=0.999, adam_eps=1e-8, decay=1e-5, alpha=1e-2, beta=1e-3, batch_size_cfg=1024)
-    a.update(over)
-    return lib.Hyper(*[a[n] for n, _ in lib.Hyper._fields_])
-
-
-def backward(lib, mem, inv, kind=None, ws_bytes=1 << 30, rows3="p", hp=None):
-    p, L = mem[1], lib.lib()
-    hp = hp or _hyper(lib)
-    call = L.macr_shard_backward_inv if inv else L.macr_shard_backward
-    return call(lib.LOSS_RUBIBCEBOTH if kind is None else kind, B, D, p if rows3 == "p" else None, p, p, p, ctypes.byref(hp), p,
-                None, None, p, ws_bytes, None)
-
-
-def forward_slice(lib, mem, inv, kind=None, ws_bytes=1 << 30, t0=32, n=64, w="p", b=B, d=D):
-    p, L = mem[1], lib.lib()
-    call = L.macr_shard_forward_slice_inv if inv else L.macr_shard_forward_slice
-    return call(lib.LOSS_RUBIBCEBOTH if kind is None else kind, b, d, t0, n, p, p if w == "p" else None, p, None, None, p, ws_bytes, None)
-
-
-def backward_slice(lib, mem, inv, kind=None, ws_bytes=1 << 30, t0=32, n=64, w="p", b=B, d=D):
-    p, L = mem[1], lib.lib()
-    hp = _hyper(lib)
-    call = L.macr_shard_backward_slice_inv if inv else L.macr_shard_backward_slice
-    return call(lib.LOSS_RUBIBCEBOTH if kind is None else kind, b, d, t0, n, p, p if w == "p" else None, p, p, ctypes.byref(hp), p, p,
-                None, None, p, ws_bytes, None)
-
-
-def apply(lib, mem, form, ws_bytes=1 << 30, u="p", lazy_period=4, n_users_loc=40):
-    """form: "plain" (macr_shard_apply), "lazy" (macr_shard_apply_lazy), "inv" (lazy = NULL), "inv_lazy" """
-    p, L = mem[1], lib.lib()
-    hp = _hyper(lib)
-    lz = lib.LazyAdam(p, p, p, lazy_period)
-    head = [lib.LOSS_RUBIBCEBOTH, B, D, n_users_loc, 50, 0, 1, 0, 1, p if u == "p" else None, p, p] + [p] * 16 + [ctypes.byref(hp)]
-    tail = [p, ws_bytes, None]
-    if form == "plain":
-        return L.macr_shard_apply(*(head + tail))
-    if form == "lazy":
-        return L.macr_shard_apply_lazy(*(head + [ctypes.byref(lz)] + tail))
-    return L.macr_shard_apply_inv(*(head + [ctypes.byref(lz) if form == "inv_lazy" else None] + tail))
+    return aligned_mem()
 
 
 # ----------------------------------------------------------------------------- the C ABI
@@ -161,10 +117,10 @@ def test_slice_inv_refuses_bad_arguments_and_too_many_blocks(lib):
 def test_backward_inv_refuses_what_backward_refuses(lib, mem):
     for over in (dict(kind=lib.LOSS_RUBIBPR), dict(kind=lib.LOSS_RUBIBCE_EGO), dict(kind=77), dict(rows3=None),
                  dict(hp=_hyper(lib, batch_size_cfg=0)), dict(hp=_hyper(lib, beta1=1.5))):
-        plain = backward(lib, mem, False, **over)
+        plain = backward(lib, mem, "plain", **over)
         assert plain == lib.E_INVALID, over
-        assert backward(lib, mem, True, **over) == plain, over
-    assert backward(lib, mem, False, ws_bytes=16) == lib.E_WORKSPACE == backward(lib, mem, True, ws_bytes=16)
+        assert backward(lib, mem, "inv", **over) == plain, over
+    assert backward(lib, mem, "plain", ws_bytes=16) == lib.E_WORKSPACE == backward(lib, mem, "inv", ws_bytes=16)
     assert b"workspace" in lib.lib().macr_last_error()
 
 
@@ -173,21 +129,21 @@ def test_slice_calls_refuse_what_their_counterparts_refuse(lib, mem, call):
     for over, code in ((dict(kind=lib.LOSS_NORMALBCE), lib.E_UNSUPPORTED), (dict(kind=lib.LOSS_BPR), lib.E_UNSUPPORTED),
                        (dict(kind=lib.LOSS_RUBIBPR), lib.E_UNSUPPORTED), (dict(w=None), lib.E_INVALID),
                        (dict(t0=288, n=50), lib.E_INVALID), (dict(t0=-32), lib.E_INVALID), (dict(ws_bytes=16), lib.E_WORKSPACE)):
-        plain = call(lib, mem, False, **over)
+        plain = call(lib, mem, "plain", **over)
         assert plain == code, over
-        assert call(lib, mem, True, **over) == plain, over
+        assert call(lib, mem, "inv", **over) == plain, over
     # of their own: a slice not cut at multiples of 32 (the end of the batch is a cut)
     for t0, n in ((10, 54), (32, 50), (0, 299)):
-        assert call(lib, mem, False, t0=t0, n=n, ws_bytes=16) == lib.E_WORKSPACE       # (the plain call has no such rule)
-        assert call(lib, mem, True, t0=t0, n=n) == lib.E_INVALID, (t0, n)
+        assert call(lib, mem, "plain", t0=t0, n=n, ws_bytes=16) == lib.E_WORKSPACE       # (the plain call has no such rule)
+        assert call(lib, mem, "inv", t0=t0, n=n) == lib.E_INVALID, (t0, n)
     for t0, n in ((0, 0), (288, 12), (0, 300), (64, 0), (96, 204)):
-        assert call(lib, mem, True, t0=t0, n=n, ws_bytes=16) == lib.E_WORKSPACE, (t0, n)   # accepted as a slice
+        assert call(lib, mem, "inv", t0=t0, n=n, ws_bytes=16) == lib.E_WORKSPACE, (t0, n)   # accepted as a slice
     # too many blocks: refused before the workspace is looked at, nothing is launched
     for d in (32, 256):
         b = 4096 * 1024 // d + 1
-        assert call(lib, mem, True, b=b, d=d, t0=0, n=64, ws_bytes=16) == lib.E_UNSUPPORTED
+        assert call(lib, mem, "inv", b=b, d=d, t0=0, n=64, ws_bytes=16) == lib.E_UNSUPPORTED
         assert b"4096 blocks" in lib.lib().macr_last_error()
-        assert call(lib, mem, True, b=b - 1, d=d, t0=0, n=64, ws_bytes=16) == lib.E_WORKSPACE
+        assert call(lib, mem, "inv", b=b - 1, d=d, t0=0, n=64, ws_bytes=16) == lib.E_WORKSPACE
 
 
 def test_branch_fold_inv_validates_before_any_launch(lib, mem):
@@ -212,10 +168,10 @@ def test_inv_calls_refuse_a_workspace_of_the_plain_size(lib, mem):
     L = lib.lib()
     plain, inv = L.macr_shard_workspace_bytes(B, D), L.macr_shard_workspace_bytes_inv(B, D)
     assert inv > plain
-    for rc in (backward(lib, mem, True, ws_bytes=plain), backward(lib, mem, True, kind=lib.LOSS_NORMALBCE, ws_bytes=plain),
-               forward_slice(lib, mem, True, ws_bytes=plain), backward_slice(lib, mem, True, ws_bytes=plain),
+    for rc in (backward(lib, mem, "inv", ws_bytes=plain), backward(lib, mem, "inv", kind=lib.LOSS_NORMALBCE, ws_bytes=plain),
+               forward_slice(lib, mem, "inv", ws_bytes=plain), backward_slice(lib, mem, "inv", ws_bytes=plain),
                apply(lib, mem, "inv", ws_bytes=plain), apply(lib, mem, "inv_lazy", ws_bytes=plain),
-               L.macr_shard_branch_fold_inv(B, D, mem[1], plain, None), backward(lib, mem, True, ws_bytes=inv - 1)):
+               L.macr_shard_branch_fold_inv(B, D, mem[1], plain, None), backward(lib, mem, "inv", ws_bytes=inv - 1)):
         assert rc == lib.E_WORKSPACE
         assert b"workspace" in L.macr_last_error()
 
