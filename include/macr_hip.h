@@ -923,6 +923,39 @@ int macr_item_counts(int U, int K, int k, const int32_t *rankings, const int32_t
                      long long *group_out, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Position-weighted exposure of a ranking (additive, abi 16): macr_item_counts with a weight per list position instead of
+ * 1 per entry, for the exposure and DCG-share report of MACR_EXPOSURE_REPORT=1 (macr_amd/exposure.py).
+ *   rankings, gt_ptr / gt_idx, n_items, group_of / n_groups: as macr_item_counts takes them; only the first k ids of a row
+ *             are read, ids < 0 or >= n_items are skipped, the ground-truth test is macr_metrics_mf's binary search
+ *   pos_weight (dev) uint32[k]: the weight of list position p (exposure.position_weights: 2^24 / log2(p + 2), rounded)
+ *   exp_w     (dev) long long[n_items] <- the sum of pos_weight[p] over the entries (u, p < k) that name the item
+ *   hit_w     (dev) long long[n_items] <- the same sum over the entries whose user's ground truth holds the item
+ *   group_out (dev, may be NULL) long long[n_groups*2] <- per group {sum of exp_w, sum of hit_w}; written when group_of and
+ *             group_out are both given; an item whose group_of value lies outside [0, n_groups) is in no group's sum
+ *   workspace (dev) >= macr_item_exposure_workspace_bytes(U, K, n_items) bytes, 16-byte aligned: MACR_ITEM_EXPOSURE_REPLICAS
+ *             copies of an {exp, hit} pair of 64-bit counters per item.  Contents need not be initialised or preserved.
+ * The call overwrites its outputs (the caller need not zero them).  Unsigned 64-bit integer sums: exact (modulo 2^64; U < 2^31
+ * entries of weight < 2^32 per item cannot overflow) and identical from run to run, whatever the order of arrival.
+ * Form: a workgroup of MACR_ITEM_EXPOSURE_TILE threads takes a CONTIGUOUS run of tiles of MACR_ITEM_EXPOSURE_TILE
+ * entries -- ceil(tiles / min(tiles, MACR_ITEM_EXPOSURE_MAX_BLOCKS)) of them -- and combines equal ids in an open-addressed LDS
+ * table of MACR_ITEM_EXPOSURE_BINS slots {id, exp, hit} (4 probes, then straight to global memory) before it adds the
+ * occupied slots into copy (block % MACR_ITEM_EXPOSURE_REPLICAS) of the workspace; a last launch sums the copies into the
+ * outputs with plain stores and forms the group sums.  Three launches, no host synchronisation.
+ * Refused before any device work: U < 1, k < 1, k > K, n_items <= 0, a null rankings / gt / weight / output pointer, group_of
+ * with n_groups outside [1, 64], a null or misaligned workspace -> MACR_E_INVALID; then a workspace too small ->
+ * MACR_E_WORKSPACE.
+ * -------------------------------------------------------------------------*/
+#define MACR_ITEM_EXPOSURE_BINS        2048   /* LDS table slots per workgroup                          */
+#define MACR_ITEM_EXPOSURE_TILE        1024   /* entries per tile = threads per workgroup               */
+#define MACR_ITEM_EXPOSURE_MAX_BLOCKS  1024   /* workgroups at most; beyond: several tiles per workgroup */
+#define MACR_ITEM_EXPOSURE_REPLICAS    8      /* copies of the per-item counter pair in the workspace   */
+size_t macr_item_exposure_workspace_bytes(int U, int K, int n_items);
+int macr_item_exposure(int U, int K, int k, const int32_t *rankings, const int32_t *gt_ptr, const int32_t *gt_idx,
+                       const uint32_t *pos_weight, int n_items, const int32_t *group_of, int n_groups,
+                       long long *exp_w, long long *hit_w, long long *group_out,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Scores and full-catalogue positions of given (query, item) pairs (additive, abi 16).  The reference's test()
  * (macr_mf/train.py:224-251) materialises the whole (U, N) score matrix and ranklist_by_sorted keeps its first K columns;
  * these two calls answer for ANY pair -- a held-out item at position 900 as well as one at position 3 -- what that

@@ -20,6 +20,9 @@ MAX_SWEEP = 4
 ABI_VERSION = 16
 LAZY_STATE_BYTES, LAZY_MAX_PERIOD = 1040, 64
 REFSTREAM_MF, REFSTREAM_LGCN = 0, 1
+# MACR_ITEM_EXPOSURE_* of include/macr_hip.h: the LDS table slots, entries per tile, workgroup cap and counter copies of
+# macr_item_exposure (a workgroup takes ceil(tiles / min(tiles, cap)) consecutive tiles)
+ITEM_EXPOSURE_BINS, ITEM_EXPOSURE_TILE, ITEM_EXPOSURE_MAX_BLOCKS, ITEM_EXPOSURE_REPLICAS = 2048, 1024, 1024, 8
 
 
 def is_pair_loss(kind):
@@ -130,6 +133,8 @@ SIGNATURES = {
     "macr_metrics_mf_mean": (_i, [_i, _i, _p, _p, _p, _p, ctypes.POINTER(ctypes.c_int32), _i, _p, _p, _p, _z, _p]),
     "macr_item_counts_workspace_bytes": (_z, [_i, _i, _i]),
     "macr_item_counts": (_i, [_i, _i, _i, _p, _p, _p, _i, _p, _i, _p, _p, _p, _p, _z, _p]),
+    "macr_item_exposure_workspace_bytes": (_z, [_i, _i, _i]),
+    "macr_item_exposure": (_i, [_i, _i, _i, _p, _p, _p, _p, _i, _p, _i, _p, _p, _p, _p, _z, _p]),
     "macr_rank_positions_workspace_bytes": (_z, [_i, _ll, _i, _i]),
     "macr_score_pairs": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _ll, _p, _p]),
     "macr_rank_positions": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _ll, _p, _p, _z, _p]),

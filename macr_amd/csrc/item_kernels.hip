@@ -107,6 +107,106 @@ __global__ __launch_bounds__(256) void k_item_finish(int n_items, const unsigned
     if (group_out && threadIdx.x < 2 * n_groups && sums[threadIdx.x]) atomicAdd(&group_out[threadIdx.x], sums[threadIdx.x]);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Position-weighted exposure (macr_item_exposure): per item the sum of pos_weight[p] over the entries (u, p < k) that name
+// it (exp_w) and over those of them whose user's ground truth holds it (hit_w).  The form of k_item_counts with 64-bit
+// sums: a slot is {key, exp, hit} = 4 + 8 + 8 bytes, so the table of kExpBins slots takes 40 KB of LDS; an entry claims
+// its slot with one LDS compare-and-swap and adds its weight to the slot's exp sum, and to its hit sum when it is a hit
+// (most entries are not: the second LDS add is skipped for them, adding zero would change nothing).  An entry whose
+// kItemProbes slots belong to other ids adds to global memory directly.  The workgroups add their occupied slots into
+// kExpReplicas copies of an {exp, hit} pair of 64-bit counters per item (16 bytes, the two adds of a flush meet one
+// cache line), and k_exposure_finish sums the copies into the outputs with plain stores.  Unlike k_item_counts a
+// workgroup takes a CONTIGUOUS run of tiles (tiles_per_block): consecutive users' lists, whose ground-truth rows are
+// neighbours too.  Unsigned 64-bit integer adds throughout: exact, and independent of the order of arrival.
+constexpr int kExpBinBits = 11, kExpBins = MACR_ITEM_EXPOSURE_BINS;      // 2048 slots x (4 + 8 + 8) B = 40 KB of LDS
+constexpr int kExpThreads = MACR_ITEM_EXPOSURE_TILE;                      // one tile = one entry per thread
+constexpr int kExpMaxBlocks = MACR_ITEM_EXPOSURE_MAX_BLOCKS;
+constexpr int kExpReplicas = MACR_ITEM_EXPOSURE_REPLICAS;
+static_assert(kExpBins == 1 << kExpBinBits, "the hash keeps kExpBinBits bits");
+static_assert(kExpThreads == 1024 && kExpBins % kExpThreads == 0, "the tile is the workgroup");
+
+// acc: kExpReplicas x n_items x {exp, hit}
+__global__ __launch_bounds__(kExpThreads) void k_item_exposure(long long n_entries, long long tiles_per_block, int K, int k, int n_items,
+                                                               const int32_t *__restrict__ rankings,
+                                                               const int32_t *__restrict__ gt_ptr, const int32_t *__restrict__ gt_idx,
+                                                               const uint32_t *__restrict__ pos_weight,
+                                                               unsigned long long *__restrict__ acc) {
+    unsigned long long *mine = acc + (size_t)(blockIdx.x % kExpReplicas) * n_items * 2;
+    __shared__ int32_t keys[kExpBins];
+    __shared__ unsigned long long exps[kExpBins];
+    __shared__ unsigned long long hits[kExpBins];
+    for (int s = threadIdx.x; s < kExpBins; s += kExpThreads) { keys[s] = -1; exps[s] = 0ull; hits[s] = 0ull; }
+    __syncthreads();
+    const long long first = (long long)blockIdx.x * tiles_per_block * kExpThreads;
+    for (long long t = 0; t < tiles_per_block; ++t) {
+        const long long e0 = first + t * kExpThreads;
+        if (e0 + threadIdx.x >= n_entries) break;         // (entries ascend with t: nothing further for this lane)
+        // the tile's first user once per wave (uniform 64-bit division), the lane's own by a 32-bit one
+        const long long u0 = n_entries <= 0x7fffffffLL ? (long long)((unsigned)e0 / (unsigned)k) : e0 / k;
+        const unsigned r = (unsigned)(e0 - u0 * k) + threadIdx.x;
+        const long long u = u0 + r / (unsigned)k;
+        const int p = (int)(r % (unsigned)k);
+        const int32_t id = rankings[(size_t)u * K + p];
+        if (id < 0 || id >= n_items) continue;            // -1 = unused slot; an id outside the catalogue is never counted
+        const int a = gt_ptr[u], b = gt_ptr[u + 1];
+        const bool hit = item_in_sorted(gt_idx + a, b - a, id);
+        const unsigned long long wgt = pos_weight[p];
+        const unsigned h = ((unsigned)id * 2654435761u) >> (32 - kExpBinBits);
+        bool binned = false;
+#pragma unroll
+        for (int probe = 0; probe < kItemProbes && !binned; ++probe) {
+            const int s = (h + probe) & (kExpBins - 1);
+            int32_t owner = keys[s];
+            if (owner == -1) owner = atomicCAS(&keys[s], -1, id);       // -1: this lane claimed the slot
+            if (owner == -1 || owner == id) {
+                atomicAdd(&exps[s], wgt);
+                if (hit) atomicAdd(&hits[s], wgt);
+                binned = true;
+            }
+        }
+        if (!binned) {
+            atomicAdd(&mine[2 * (size_t)id], wgt);
+            if (hit) atomicAdd(&mine[2 * (size_t)id + 1], wgt);
+        }
+    }
+    __syncthreads();
+    for (int s = threadIdx.x; s < kExpBins; s += kExpThreads) {
+        const int32_t id = keys[s];
+        if (id < 0) continue;
+        if (exps[s]) atomicAdd(&mine[2 * (size_t)id], exps[s]);
+        if (hits[s]) atomicAdd(&mine[2 * (size_t)id + 1], hits[s]);
+    }
+}
+
+// exp_w[i], hit_w[i] = the sum of item i's copies (plain stores: the outputs need no zero-fill), and with group_of
+// group_out[2 g] += exp, group_out[2 g + 1] += hit over the items of group g (LDS bins, one global add per block and sum)
+__global__ __launch_bounds__(256) void k_exposure_finish(int n_items, const ulonglong2 *__restrict__ acc,
+                                                         const int32_t *__restrict__ group_of, int n_groups,
+                                                         unsigned long long *__restrict__ exp_w, unsigned long long *__restrict__ hit_w,
+                                                         unsigned long long *__restrict__ group_out) {
+    __shared__ unsigned long long sums[128];
+    if (threadIdx.x < 128) sums[threadIdx.x] = 0ull;
+    __syncthreads();
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_items; i += gridDim.x * blockDim.x) {
+        unsigned long long e = 0ull, h = 0ull;
+#pragma unroll
+        for (int r = 0; r < kExpReplicas; ++r) {
+            const ulonglong2 c = acc[(size_t)r * n_items + i];
+            e += c.x;
+            h += c.y;
+        }
+        exp_w[i] = e;
+        hit_w[i] = h;
+        if (!group_out || e == 0) continue;               // (hit <= exp: nothing to add either)
+        const int g = group_of[i];
+        if (g < 0 || g >= n_groups) continue;             // an item outside every group is in no sum
+        atomicAdd(&sums[2 * g], e);
+        if (h) atomicAdd(&sums[2 * g + 1], h);
+    }
+    __syncthreads();
+    if (group_out && threadIdx.x < 2 * n_groups && sums[threadIdx.x]) atomicAdd(&group_out[threadIdx.x], sums[threadIdx.x]);
+}
+
 }  // namespace macr
 
 using namespace macr;
@@ -145,5 +245,47 @@ extern "C" int macr_item_counts(int U, int K, int k, const int32_t *rankings, co
     k_item_finish<<<fb, 256, 0, st>>>(n_items, packed, groups ? group_of : nullptr, n_groups, rec_cnt, hit_cnt,
                                       groups ? reinterpret_cast<unsigned long long *>(group_out) : nullptr);
     MACR_CHECK_LAUNCH("item_finish", st);
+    return MACR_OK;
+}
+
+extern "C" size_t macr_item_exposure_workspace_bytes(int U, int K, int n_items) {
+    if (U <= 0 || K < 1 || n_items <= 0) return 0;
+    return (size_t)kExpReplicas * (size_t)n_items * 2 * sizeof(unsigned long long);
+}
+
+extern "C" int macr_item_exposure(int U, int K, int k, const int32_t *rankings, const int32_t *gt_ptr, const int32_t *gt_idx,
+                                  const uint32_t *pos_weight, int n_items, const int32_t *group_of, int n_groups,
+                                  long long *exp_w, long long *hit_w, long long *group_out, void *workspace, size_t workspace_bytes,
+                                  void *stream) {
+    hipStream_t st = as_stream(stream);
+    MACR_REQUIRE(U > 0 && K >= 1, MACR_E_INVALID, "item_exposure: U=%d K=%d", U, K);
+    MACR_REQUIRE(k >= 1 && k <= K, MACR_E_INVALID, "item_exposure: k=%d outside [1, K=%d]", k, K);
+    MACR_REQUIRE(n_items > 0, MACR_E_INVALID, "item_exposure: n_items=%d", n_items);
+    MACR_REQUIRE(rankings && gt_ptr && gt_idx && pos_weight && exp_w && hit_w, MACR_E_INVALID, "item_exposure: null pointer");
+    MACR_REQUIRE(!group_of || (n_groups >= 1 && n_groups <= 64), MACR_E_INVALID,
+                 "item_exposure: group_of given with n_groups=%d outside [1,64]", n_groups);
+    MACR_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, MACR_E_INVALID,
+                 "item_exposure: workspace is null or not 16-byte aligned (macr_item_exposure_workspace_bytes)");
+    MACR_REQUIRE(workspace_bytes >= macr_item_exposure_workspace_bytes(U, K, n_items), MACR_E_WORKSPACE,
+                 "item_exposure: workspace %zu < %zu bytes", workspace_bytes, macr_item_exposure_workspace_bytes(U, K, n_items));
+    const bool groups = group_of && group_out;
+    unsigned long long *acc = static_cast<unsigned long long *>(workspace);
+    const size_t n_words = (size_t)kExpReplicas * n_items * 2;
+    const size_t zb = (n_words + 256 * 8 - 1) / (256 * 8);
+    k_item_zero<<<(unsigned)(zb < 2048 ? zb : 2048), 256, 0, st>>>(acc, n_words, groups ? group_out : nullptr, groups ? 2 * n_groups : 0);
+    MACR_CHECK_LAUNCH("exposure_zero", st);
+    const long long n_entries = (long long)U * k;
+    const long long tiles = (n_entries + kExpThreads - 1) / kExpThreads;
+    const long long cap = tiles < kExpMaxBlocks ? tiles : kExpMaxBlocks;
+    const long long tiles_per_block = (tiles + cap - 1) / cap;
+    const long long blocks = (tiles + tiles_per_block - 1) / tiles_per_block;       // <= cap; every block has a tile
+    k_item_exposure<<<(unsigned)blocks, kExpThreads, 0, st>>>(n_entries, tiles_per_block, K, k, n_items, rankings, gt_ptr, gt_idx,
+                                                              pos_weight, acc);
+    MACR_CHECK_LAUNCH("item_exposure", st);
+    const int fb = (n_items + 255) / 256 < 1024 ? (n_items + 255) / 256 : 1024;
+    k_exposure_finish<<<fb, 256, 0, st>>>(n_items, reinterpret_cast<const ulonglong2 *>(acc), groups ? group_of : nullptr, n_groups,
+                                          reinterpret_cast<unsigned long long *>(exp_w), reinterpret_cast<unsigned long long *>(hit_w),
+                                          groups ? reinterpret_cast<unsigned long long *>(group_out) : nullptr);
+    MACR_CHECK_LAUNCH("exposure_finish", st);
     return MACR_OK;
 }

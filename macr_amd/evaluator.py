@@ -264,6 +264,15 @@ class Evaluator(object):
         gv, gi = sharding.gather_topk(lv, li)                        # (W,U,K) over RCCL / xGMI
         return ops.topk_merge(gv, gi, fill)
 
+    def _groups_on_device(self, group_of, n_groups):
+        """(int32 device tensor of the items' group ids or None, n_groups; None: max + 1)"""
+        if group_of is None:
+            return None, n_groups
+        group_of = torch.as_tensor(np.asarray(group_of.cpu() if torch.is_tensor(group_of) else group_of), dtype=torch.int32)
+        if n_groups is None:
+            n_groups = int(group_of.max()) + 1
+        return group_of.to(self.device).contiguous(), n_groups
+
     # ------------------------------------------------------------------ per-item diagnostic (--out 1)
     def item_accuracy(self, kind, users_tab, user_ids, items_tab, k, w=None, wu=None, c=0.0, branch=None, group_of=None,
                       n_groups=None):
@@ -276,12 +285,27 @@ class Evaluator(object):
         rank()'s all-gather: correct under item sharding without a collective of its own."""
         depth = max(int(k), getattr(self, "_last_depth", 0))
         _, idx, _ = self.rank(kind, users_tab, user_ids, items_tab, depth, w, wu, c, fill_masked=False, branch=branch)
-        if group_of is not None:
-            group_of = torch.as_tensor(np.asarray(group_of.cpu() if torch.is_tensor(group_of) else group_of), dtype=torch.int32)
-            if n_groups is None:
-                n_groups = int(group_of.max()) + 1
-            group_of = group_of.to(self.device).contiguous()
+        group_of, n_groups = self._groups_on_device(group_of, n_groups)
         return ops.item_counts(idx, self.gt, k, self.n_items, group_of, n_groups or 0)
+
+    # ------------------------------------------------------------------ exposure report (MACR_EXPOSURE_REPORT=1)
+    def item_exposure(self, kind, users_tab, user_ids, items_tab, k, w=None, wu=None, c=0.0, branch=None, group_of=None,
+                      n_groups=None):
+        """What exposure.summarize needs of the ranking an evaluation with the same arguments scores:
+        (rec_cnt, exp_w, hit_w, group_sums) on the device -- int32[n_items] users whose k best non-train items contain the
+        item (item_accuracy's rec_cnt), int64[n_items] the sum of exposure.position_weights(k)[p] over those list entries
+        and over the hits among them, and with group_of (n_items group ids, 0 .. n_groups-1; n_groups None: max + 1) the
+        int64 (n_groups, 2) {exp, hit} sums per group, else None.  Ranked as item_accuracy ranks (rank() without the -inf
+        fill, at the evaluator's last depth when that is deeper than k) and counted on the MERGED ranking, which every
+        rank holds after rank()'s all-gather: correct under item sharding (several ranks, set_local_items) without a
+        collective of its own.  Integer sums: the same bytes for every number of ranks."""
+        from . import exposure
+        depth = max(int(k), getattr(self, "_last_depth", 0))
+        _, idx, _ = self.rank(kind, users_tab, user_ids, items_tab, depth, w, wu, c, fill_masked=False, branch=branch)
+        group_of, n_groups = self._groups_on_device(group_of, n_groups)
+        rec, _, _ = ops.item_counts(idx, self.gt, k, self.n_items)
+        exp_w, hit_w, sums = ops.item_exposure(idx, self.gt, exposure.position_weights(k), self.n_items, group_of, n_groups or 0)
+        return rec, exp_w, hit_w, sums
 
     # ------------------------------------------------------------------ full-catalogue positions (MACR_RANK_REPORT=1)
     def rank_positions(self, kind, users_tab, user_ids, items_tab, w=None, wu=None, c=0.0, branch=None):

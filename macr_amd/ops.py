@@ -7,6 +7,7 @@ a CPU or eager-PyTorch fallback -- CPU tensors are rejected.
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -520,6 +521,46 @@ def item_counts(rankings, gt, k, n_items, group_of=None, n_groups=0):
                              _ptr(group_of, _i32, True), int(n_groups), _ptr(rec), _ptr(hit), _ptr(sums, None, True),
                              _ptr(ws, None, True), need, _stream()))
     return rec, hit, sums
+
+
+_pos_weight_cache = {}
+
+
+def _position_weights_on(weights, device):
+    """uint32 position weights as a device tensor (int32 storage, the same bits); one upload per distinct vector and device"""
+    if torch.is_tensor(weights):
+        weights = weights.cpu().numpy()
+    w = np.asarray(weights)
+    if w.ndim != 1 or w.size < 1 or (w.astype(np.int64) < 0).any() or (w.astype(np.int64) >> 32).any():
+        raise MacrError(_lib.E_INVALID, "item_exposure: the position weights are a non-empty vector of values in [0, 2^32)")
+    w = np.ascontiguousarray(w.astype(np.uint32))
+    key = (w.tobytes(), str(device))
+    t = _pos_weight_cache.get(key)
+    if t is None:
+        if len(_pos_weight_cache) >= 16:
+            _pos_weight_cache.clear()
+        t = _pos_weight_cache[key] = torch.from_numpy(w.view(np.int32)).to(device)
+    return t
+
+
+def item_exposure(rankings, gt, weights, n_items, group_of=None, n_groups=0):
+    """(U,K) ranked ids (-1 = unused slot) + ground-truth CSR + uint32[k] position weights -> (exp_w, hit_w, group_sums):
+    int64[n_items] the sum of weights[p] over the entries (u, p < k) that name the item / over those of them whose user's
+    ground truth holds it (macr_item_exposure: item_counts with a weight per position, k = len(weights)), and with group_of
+    (int32[n_items], values 0 .. n_groups-1) the int64 (n_groups, 2) {exp, hit} sums per group, else None.  Exact integers."""
+    U, K = rankings.shape
+    L = _lib.lib()
+    dev = rankings.device
+    w = _position_weights_on(weights, dev)
+    exp_w = torch.empty(n_items, dtype=torch.int64, device=dev)
+    hit_w = torch.empty(n_items, dtype=torch.int64, device=dev)
+    sums = torch.empty((n_groups, 2), dtype=torch.int64, device=dev) if group_of is not None else None
+    need = L.macr_item_exposure_workspace_bytes(U, K, n_items)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    check(L.macr_item_exposure(U, K, int(w.numel()), _ptr(rankings, _i32), _ptr(gt.ptr, _i32), _ptr(gt.idx, _i32), _ptr(w, _i32),
+                               int(n_items), _ptr(group_of, _i32, True), int(n_groups), _ptr(exp_w), _ptr(hit_w),
+                               _ptr(sums, None, True), _ptr(ws, None, True), need, _stream()))
+    return exp_w, hit_w, sums
 
 
 def score_pairs(kind, users_tab, user_ids, items, pairs, sig_u=None, sig_i=None, c=0.0, n_pairs=None):

@@ -10,7 +10,7 @@ import torch
 
 from utility import batch_test as _bt
 
-from macr_amd import ops, popularity, rank_report, sharding
+from macr_amd import exposure, ops, popularity, rank_report, sharding
 from macr_amd.eval_cache import EvaluatorCache
 from macr_amd.evaluator import Evaluator
 
@@ -50,11 +50,14 @@ def test(sess, model, users_to_test, drop_flag=False, train_set_flag=0, method="
         item_diagnostic(sess, model, users_to_test, method)
     if rank_report.enabled():
         rank_diagnostic(sess, model, users_to_test, method)
+    if exposure.enabled():
+        exposure_diagnostic(sess, model, users_to_test, method)
     return ret
 
 
 def _popularity_tables():
-    """{'group_of': the popularity group of every item, 'n_test': its test interactions}, built once"""
+    """{'group_of': the popularity group of every item, 'n_test': its test interactions, 'train_counts': its train
+    interactions}, built once"""
     if not _popularity:
         data = _bt.data_generator
         counts = np.zeros(_bt.ITEM_NUM, dtype=np.int64)
@@ -63,7 +66,7 @@ def _popularity_tables():
         n_test = np.zeros(_bt.ITEM_NUM, dtype=np.int64)
         for item, users in data.test_item_set.items():
             n_test[item] = len(users)
-        _popularity.update(group_of=popularity.item_groups(counts), n_test=n_test)
+        _popularity.update(group_of=popularity.item_groups(counts), n_test=n_test, train_counts=counts)
     return _popularity
 
 
@@ -80,6 +83,25 @@ def rank_diagnostic(sess, model, users_to_test, method):
                                 group_of=_popularity_tables()["group_of"], n_groups=len(popularity.POINTS) + 1)
     if sharding.is_main():
         print(rank_report.format_line(rep))
+
+
+def exposure_diagnostic(sess, model, users_to_test, method):
+    """MACR_EXPOSURE_REPORT=1: one line on the concentration of the top-max(Ks) lists test() ranks with the same arguments (same
+    score kind, the model's current c -- after a sweep the chosen one): catalogue coverage, Gini, average recommendation
+    popularity, each also with every slot weighted by 1 / log2(position + 2), and the train-popularity groups' shares of
+    that exposure and of the DCG mass of the hits (macr_amd/exposure.py).  Every rank ranks; the main rank prints."""
+    one_branch = method in _ITEM_BRANCH
+    evaluator, uid = (_evaluator_for if one_branch else _bt._evaluator_for)(model, users_to_test)
+    kind = ops.SCORE_RUBI if one_branch else _bt._METHODS[method]
+    tables = _popularity_tables()
+    k, n_groups = max(model.Ks), len(popularity.POINTS) + 1
+    ua, ia = model.propagated()
+    rec, exp_w, hit_w, _ = evaluator.item_exposure(kind, ua, uid, ia.contiguous(), k, model.w, model.w_user, model.rubi_c,
+                                                   branch=_branch(model, method) if one_branch else None,
+                                                   group_of=tables["group_of"], n_groups=n_groups)
+    if sharding.is_main():
+        print(exposure.format_line(exposure.summarize(rec.cpu().numpy(), exp_w.cpu().numpy(), hit_w.cpu().numpy(),
+                                                      tables["train_counts"], tables["group_of"], n_groups, len(users_to_test), k)))
 
 
 def item_diagnostic(sess, model, users_to_test, method):

@@ -24,7 +24,7 @@ import torch
 from batch_test import *          # noqa: F401,F403  (args, data, Ks, BATCH_SIZE, ITEM_NUM, USER_NUM)
 from model import BPRMF, Session
 
-from macr_amd import ops, popularity, rank_report
+from macr_amd import exposure, ops, popularity, rank_report
 from macr_amd.evaluator import Evaluator
 from macr_amd.eval_cache import EvaluatorCache
 from macr_amd.metrics_host import (precision_at_k, dcg_at_k, ndcg_at_k, recall_at_k, hit_at_k,   # noqa: F401
@@ -72,6 +72,8 @@ def test(sess, model, test_users, batch_test_flag=False, model_type='o', valid_s
         item_diagnostic(sess, model, test_users, model_type, valid_set)
     if rank_report.enabled():
         rank_diagnostic(sess, model, test_users, model_type, valid_set)
+    if exposure.enabled():
+        exposure_diagnostic(sess, model, test_users, model_type, valid_set)
     return ret
 
 
@@ -119,6 +121,28 @@ def rank_diagnostic(sess, model, test_users, model_type='o', valid_set="test"):
                                 model.rubi_c, group_of=_n_test["groups"], n_groups=len(rate))
     if sharding.is_main():
         print(rank_report.format_line(rep))
+
+
+def exposure_diagnostic(sess, model, test_users, model_type='o', valid_set="test"):
+    """MACR_EXPOSURE_REPORT=1: one line on the concentration of the top-max(Ks) lists test() ranks with the same arguments (same
+    score kind, the model's current c) -- catalogue coverage, Gini, average recommendation popularity, each also with every
+    slot weighted by 1 / log2(position + 2), and the train-popularity groups' shares of that exposure and of the DCG mass
+    of the hits (macr_amd/exposure.py).  Counted on the merged ranking: every rank ranks (also under --row_shard 1), the
+    main rank prints."""
+    from macr_amd import sharding
+    evaluator, uid = _evaluator_for(model, test_users, valid_set)
+    model.sync()
+    if "exposure" not in _n_test:
+        counts = popularity.train_counts(data.train_item_list, ITEM_NUM)
+        _n_test["exposure"] = (counts, popularity.item_groups(counts))
+    counts, group_of = _n_test["exposure"]
+    k, n_groups = max(Ks), len(popularity.POINTS) + 1
+    users_tab, ids = (model.query_rows(uid), None) if getattr(model, "sharded", False) else (model.user_embedding, uid)
+    rec, exp_w, hit_w, _ = evaluator.item_exposure(_MODEL_TYPES[model_type], users_tab, ids, model.item_embedding, k,
+                                                   model.w, model.w_user, model.rubi_c, group_of=group_of, n_groups=n_groups)
+    if sharding.is_main():
+        print(exposure.format_line(exposure.summarize(rec.cpu().numpy(), exp_w.cpu().numpy(), hit_w.cpu().numpy(), counts,
+                                                      group_of, n_groups, len(test_users), k)))
 
 
 def test_sweep(sess, model, test_users, cs, model_type='rubi_both', valid_set="test"):
@@ -335,12 +359,14 @@ def main(sweep=False):
                 if ret['hit_ratio'][0] > best[0]:
                     best = (ret['hit_ratio'][0], ret['recall'][0], ret['precision'][0], ret['ndcg'][0], c)
             ret['hit_ratio'][0], ret['recall'][0], ret['precision'][0], ret['ndcg'][0] = best[:4]
-            if sweep and (args.out == 1 or rank_report.enabled()):       # the diagnostics of the chosen c only (no hit at any c: the last one)
+            if sweep and (args.out == 1 or rank_report.enabled() or exposure.enabled()):    # the diagnostics of the chosen c only (no hit at any c: the last one)
                 model.update_c(sess, best[4] if best[0] > 0 else c_values[-1])
                 if args.out == 1:
                     item_diagnostic(sess, model, users_to_test, rubi_type, args.valid_set)
                 if rank_report.enabled():
                     rank_diagnostic(sess, model, users_to_test, rubi_type, args.valid_set)
+                if exposure.enabled():
+                    exposure_diagnostic(sess, model, users_to_test, rubi_type, args.valid_set)
                 model.update_c(sess, c_values[-1])   # (what the loop left, and what a checkpoint records)
             if best[0] > config['best_c_hr']:
                 config['best_c_hr'], config['best_c'], config['best_c_epoch'] = best[0], best[4], epoch
