@@ -995,6 +995,51 @@ int macr_rank_positions(int score_kind, int U, int n_local, int d,
                         const int32_t *pair_ptr, const int32_t *pair_item, long long n_pairs,
                         int32_t *out_pos, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * The same positions where the catalogue is cut into item shards (additive, abi 16): one rank holds the rows of the
+ * shard (item_lo, item_stride, n_local) -- local row l of `items` / sig_i is global item item_lo + l * item_stride -- and the
+ * shards of all ranks partition [0, N).  A position is an integer count over the catalogue, so it is the sum of the
+ * shards' counts once every shard compares against the same (score, GLOBAL id) key.  Pair ids and mask ids are global ids
+ * everywhere; the kernels test ownership.  users_tab ... score_kind, pair_ptr / pair_item, mask_ptr / mask_idx: as in
+ * macr_rank_positions.  Three calls with an element-wise int64 SUM over the ranks after each of the first two:
+ * macr_rank_shard_keys: out_keys[p] (dev, uint64[n_pairs]) <- the pair's key (exact score, global id) where this shard owns
+ *   the pair's item, all-ones where it owns it and the score is NaN, 0 where it does not own it (no real key is 0: its low
+ *   word would name id -1).  The sum over the ranks is x + 0 + ... + 0: exact, whatever the order; it is the COMPLETE key
+ *   array, 0 = no shard owns the item, all-ones = NaN.  One launch.
+ * macr_rank_shard_counts: given the complete keys, out_cnt[p] (dev, long long[n_pairs]) <- the number of this shard's items
+ *   i with (s_qi, global i) before the key, minus the shard's own mask items of q that are before it (a repeated entry once),
+ *   plus MACR_RANK_SHARD_MASKED where this shard owns the pair's item and q masks it; 0 for a key of 0 or all-ones; a
+ *   NaN-scoring candidate is before nothing.  The counts of all shards sum to less than 2^31, so the flag bit is safe, and
+ *   at most one rank sets it.  workspace (dev) >= macr_rank_shard_workspace_bytes(U, n_pairs, n_local, d) bytes (0:
+ *   unsupported d or bad sizes), 16-byte aligned; neither it nor out_cnt need be initialised.  Four launches, no host
+ *   synchronisation: the counters' reset, the cut into columns of 16, the counting pass of macr_rank_positions over the
+ *   shard's rows (float compare on the hot path; the tie path orders by item_lo + item_stride * local row), the finishing pass
+ *   with the ownership test on every mask entry.
+ * macr_rank_shard_combine: out_pos[p] (dev, int32[n_pairs]) <- -1 where the key is 0 or all-ones or the summed count carries
+ *   the flag bit, else the low 31 bits of the sum: macr_rank_positions' output on the whole table.  One launch.
+ * Refused before any device work, as macr_rank_positions refuses: a bad score_kind, U < 1, n_local < 1, n_pairs < 0 or
+ * > 2^31 - 1, item_lo < 0, item_stride < 1, a null table / pair / key / output pointer, a missing sig_i / sig_u, mask_ptr
+ * without mask_idx, a null or misaligned workspace -> MACR_E_INVALID; d outside {32,64,128,256} -> MACR_E_UNSUPPORTED; a
+ * workspace too small -> MACR_E_WORKSPACE.
+ * -------------------------------------------------------------------------*/
+#define MACR_RANK_SHARD_MASKED (1LL << 40)   /* in a shard's count: it owns the pair's item and the query masks it */
+size_t macr_rank_shard_workspace_bytes(int U, long long n_pairs, int n_local, int d);
+int macr_rank_shard_keys(int score_kind, int U, int n_local, int d,
+                         const float *users_tab, const int32_t *user_ids, const float *items,
+                         const float *sig_u, const float *sig_i, float c, const float *c_dev,
+                         int item_lo, int item_stride,
+                         const int32_t *pair_ptr, const int32_t *pair_item, long long n_pairs,
+                         uint64_t *out_keys, void *stream);
+int macr_rank_shard_counts(int score_kind, int U, int n_local, int d,
+                           const float *users_tab, const int32_t *user_ids, const float *items,
+                           const float *sig_u, const float *sig_i, float c, const float *c_dev,
+                           int item_lo, int item_stride,
+                           const int32_t *mask_ptr, const int32_t *mask_idx,
+                           const int32_t *pair_ptr, const uint64_t *keys, long long n_pairs,
+                           long long *out_cnt, void *workspace, size_t workspace_bytes, void *stream);
+int macr_rank_shard_combine(long long n_pairs, const uint64_t *keys, const long long *summed_cnt,
+                            int32_t *out_pos, void *stream);
+
 /* Column means of a (rows, cols) matrix in float64 (deterministic tree):
  * the "/ n_test_users" accumulation of macr_mf/train.py:286-290 and the
  * np.mean(all_result, axis=0) of batch_test.py:151.  in_is_f32 selects input

@@ -23,6 +23,7 @@ REFSTREAM_MF, REFSTREAM_LGCN = 0, 1
 # MACR_ITEM_EXPOSURE_* of include/macr_hip.h: the LDS table slots, entries per tile, workgroup cap and counter copies of
 # macr_item_exposure (a workgroup takes ceil(tiles / min(tiles, cap)) consecutive tiles)
 ITEM_EXPOSURE_BINS, ITEM_EXPOSURE_TILE, ITEM_EXPOSURE_MAX_BLOCKS, ITEM_EXPOSURE_REPLICAS = 2048, 1024, 1024, 8
+RANK_SHARD_MASKED = 1 << 40       # MACR_RANK_SHARD_MASKED: in a shard's count, "it owns the pair's item and the query masks it"
 
 
 def is_pair_loss(kind):
@@ -138,6 +139,10 @@ SIGNATURES = {
     "macr_rank_positions_workspace_bytes": (_z, [_i, _ll, _i, _i]),
     "macr_score_pairs": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _ll, _p, _p]),
     "macr_rank_positions": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _ll, _p, _p, _z, _p]),
+    "macr_rank_shard_workspace_bytes": (_z, [_i, _ll, _i, _i]),
+    "macr_rank_shard_keys": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _i, _i, _p, _p, _ll, _p, _p]),
+    "macr_rank_shard_counts": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _i, _i, _p, _p, _p, _p, _ll, _p, _p, _z, _p]),
+    "macr_rank_shard_combine": (_i, [_ll, _p, _p, _p, _p]),
     "macr_colmean": (_i, [_p, _i, _i, _i, _p, _p]),
 }
 

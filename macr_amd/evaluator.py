@@ -314,29 +314,108 @@ class Evaluator(object):
         evaluation with the same arguments ranks by (score descending, ties by ascending id): the index rank() would
         give the item with K large enough, wherever it stands.  -1: the item is also a train item of the query, or scores
         NaN.  The branch factors are computed as rank() computes them (branch: the ego item rows of LightGCN's rubi2).
-        One item shard only: the counts of several shards would have to be added (NotImplementedError)."""
+        One item shard only (NotImplementedError otherwise): rank_positions_sharded adds the counts of several shards."""
         if sharding.world()[1] > 1 or self._local_own is not None or self.local_items_range is not None:
             raise NotImplementedError("Evaluator.rank_positions ranks a whole, replicated item table: item-sharded "
                                       "evaluation (several ranks, set_local_items) has no position count yet")
         if items_tab.shape[0] != self.n_items:
             raise _lib.MacrError(_lib.E_INVALID, "rank_positions: %d item rows for an evaluator of %d items" % (items_tab.shape[0], self.n_items))
+        sig_u, sig_i = self._branch_factors(kind, users_tab, user_ids, items_tab if branch is None else branch, w, wu)
+        return ops.rank_positions(kind, users_tab, user_ids, items_tab, self.gt, sig_u, sig_i, c, self.mask, n_pairs=self.n_gt)
+
+    @staticmethod
+    def _branch_factors(kind, users_tab, user_ids, branch_tab, w, wu):
+        """(sig_u, sig_i) of a position count: sigmoid(e_u . w_user) of the queries, sigmoid(row . w) of branch_tab's rows"""
         sig_u = sig_i = None
         both = kind in (ops.SCORE_RUBI_BOTH, ops.SCORE_DIRECT_MINUS_BOTH)
-        branch_tab = items_tab if branch is None else branch
         if both and branch_tab.shape[1] == users_tab.shape[1]:
             sig_i, sig_u = ops.branch_sigmoid2(branch_tab, w, None, users_tab, wu, user_ids)
         elif kind != ops.SCORE_NORMAL:
             sig_i = ops.branch_sigmoid(branch_tab, w)
             if both:
                 sig_u = ops.branch_sigmoid(users_tab, wu, user_ids)
-        return ops.rank_positions(kind, users_tab, user_ids, items_tab, self.gt, sig_u, sig_i, c, self.mask, n_pairs=self.n_gt)
+        return sig_u, sig_i
 
     def rank_report(self, kind, users_tab, user_ids, items_tab, w=None, wu=None, c=0.0, branch=None, group_of=None, n_groups=None):
         """rank_report.summarize of rank_positions: {'users', 'pairs', 'skipped', 'auc', 'mrr', 'mpr'} and, with group_of
         (n_items group ids), 'group_pairs' / 'group_mpr' -- AUC, reciprocal rank and rank percentile of the held-out
         items over the whole catalogue, not the first K.  One device-to-host copy (the positions)."""
+        pos = self.rank_positions(kind, users_tab, user_ids, items_tab, w, wu, c, branch)
+        return self._summarize_positions(pos, group_of, n_groups)
+
+    # ------------------------------------------------------------------ the same over item shards (MACR_SHARD_RANK_REPORT=1)
+    def _rank_shard(self, kind, users_tab, user_ids, items_tab, w, wu, branch, whole_factors=None):
+        """This rank's shard for a position count, resolved as rank_local resolves it -- a replicated table cut by
+        item_shard_range, local_items_range, the strided set_local_items -- as the arguments of ops.rank_shard_*:
+        (rows of the shard or None when it is empty, sig_u, sig_i, item_lo, item_stride); the branch factors are those of
+        the shard's rows (branch: sharded like items_tab).  whole_factors: (sig_u, sig_i) of a replicated table's rows,
+        already computed -- the shard takes its slice instead of launching them again."""
+        lo, hi, rows = self._shard(items_tab)
+        if self._local_own is not None:
+            lo, stride = self._local_own.lo, self._local_own.stride
+        else:
+            if self.local_items_range is None and items_tab.shape[0] != self.n_items:
+                raise _lib.MacrError(_lib.E_INVALID, "rank_positions_sharded: %d item rows for an evaluator of %d items"
+                                     % (items_tab.shape[0], self.n_items))
+            stride = 1
+        if rows.shape[0] == 0:
+            return None, None, None, lo, stride
+        if whole_factors is not None:
+            sig_u, sig_i = whole_factors[0], None if whole_factors[1] is None else whole_factors[1][lo:hi]
+        else:
+            sig_u, sig_i = self._branch_factors(kind, users_tab, user_ids, rows if branch is None else self._shard(branch)[2], w, wu)
+        return rows, sig_u, sig_i, lo, stride
+
+    def rank_shard_keys(self, kind, users_tab, user_ids, items_tab, w=None, wu=None, c=0.0, branch=None, shard=None):
+        """First phase of rank_positions_sharded on this rank's shard: int64[n_gt], the (score, GLOBAL id) key of every
+        held-out pair whose item the shard holds, 0 elsewhere (ops.rank_shard_keys); the sum over the ranks is complete.
+        shard: what _rank_shard returned for these arguments, where the caller has it (one set of branch factors for
+        both phases)."""
+        rows, sig_u, sig_i, lo, stride = shard or self._rank_shard(kind, users_tab, user_ids, items_tab, w, wu, branch)
+        if rows is None:
+            return torch.zeros(self.n_gt, dtype=torch.int64, device=self.device)
+        return ops.rank_shard_keys(kind, users_tab, user_ids, rows, self.gt, sig_u, sig_i, c, lo, stride, n_pairs=self.n_gt)
+
+    def rank_shard_counts(self, keys, kind, users_tab, user_ids, items_tab, w=None, wu=None, c=0.0, branch=None, shard=None):
+        """Second phase: int64[n_gt], this shard's share of every pair's position given the complete keys -- its items
+        before the key, minus those of them the query's train list (the GLOBAL mask) holds, flagged where the shard holds
+        the pair's item and the train list holds it too (ops.rank_shard_counts).  shard: as in rank_shard_keys."""
+        rows, sig_u, sig_i, lo, stride = shard or self._rank_shard(kind, users_tab, user_ids, items_tab, w, wu, branch)
+        if rows is None:
+            return torch.zeros(self.n_gt, dtype=torch.int64, device=self.device)
+        return ops.rank_shard_counts(kind, users_tab, user_ids, rows, self.gt, keys, sig_u, sig_i, c, self.mask, lo, stride,
+                                     n_pairs=self.n_gt)
+
+    def rank_positions_sharded(self, kind, users_tab, user_ids, items_tab, w=None, wu=None, c=0.0, branch=None):
+        """rank_positions for any item sharding: int32[n_gt] on the device, the same on every rank and equal to what
+        rank_positions returns from one rank on the whole table.  Every rank calls it (two all-reduces of 8 bytes per pair:
+        the keys, the counts); in a world of one rank with the whole table it is rank_positions by other kernels.  A
+        position is a count over the catalogue and the shards partition it: the shards' integer counts against one
+        (score, global id) key add up, in any order.  A replicated table needs no key exchange: model.sync() and
+        broadcast_params have made the replicas equal, so every rank scores the pairs on the whole table itself.  The
+        branch factors are launched once and serve both phases."""
+        if self.n_gt == 0:
+            return torch.empty(0, dtype=torch.int32, device=self.device)
+        args = (kind, users_tab, user_ids, items_tab, w, wu, c, branch)
+        if self._local_own is None and self.local_items_range is None:
+            whole = self._branch_factors(kind, users_tab, user_ids, items_tab if branch is None else branch, w, wu)
+            shard = self._rank_shard(kind, users_tab, user_ids, items_tab, w, wu, branch, whole_factors=whole)
+            keys = ops.rank_shard_keys(kind, users_tab, user_ids, items_tab, self.gt, whole[0], whole[1], c, 0, 1, n_pairs=self.n_gt)
+        else:
+            shard = self._rank_shard(kind, users_tab, user_ids, items_tab, w, wu, branch)
+            keys = sharding.sum_over_ranks(self.rank_shard_keys(*args, shard=shard))
+        counts = sharding.sum_over_ranks(self.rank_shard_counts(keys, *args, shard=shard))
+        return ops.rank_shard_combine(keys, counts)
+
+    def rank_report_sharded(self, kind, users_tab, user_ids, items_tab, w=None, wu=None, c=0.0, branch=None, group_of=None,
+                            n_groups=None):
+        """rank_report with rank_positions_sharded underneath: the same dict on every rank, for any item sharding"""
+        pos = self.rank_positions_sharded(kind, users_tab, user_ids, items_tab, w, wu, c, branch)
+        return self._summarize_positions(pos, group_of, n_groups)
+
+    def _summarize_positions(self, pos, group_of, n_groups):
         from . import rank_report
-        pos = self.rank_positions(kind, users_tab, user_ids, items_tab, w, wu, c, branch).cpu().numpy()
+        pos = pos.cpu().numpy()
         if getattr(self, "_gt_host", None) is None:
             mask_len = np.array([len(set(row)) for row in self._mask_lists], dtype=np.int64)
             self._gt_host = (self.gt.ptr.cpu().numpy(), self.gt.idx[:self.n_gt].cpu().numpy(), self.n_items - mask_len)

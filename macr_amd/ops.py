@@ -635,6 +635,63 @@ def rank_positions(kind, users_tab, user_ids, items, pairs, sig_u=None, sig_i=No
     return out
 
 
+def _rank_shard_args(name, users_tab, user_ids, pairs, mask, n_pairs, item_lo, item_stride):
+    U = users_tab.shape[0] if user_ids is None else user_ids.numel()
+    if pairs.ptr.numel() != U + 1 or (mask is not None and mask.ptr.numel() != U + 1):
+        raise MacrError(_lib.E_INVALID, "%s: the pair / mask CSR does not have one row per query (%d)" % (name, U))
+    return U, (pairs.idx.numel() if n_pairs is None else int(n_pairs)), int(item_lo), int(item_stride)
+
+
+def rank_shard_keys(kind, users_tab, user_ids, items, pairs, sig_u=None, sig_i=None, c=0.0, item_lo=0, item_stride=1, n_pairs=None):
+    """int64[n_pairs]: this shard's part of the pairs' keys (macr_rank_shard_keys).  `items` / sig_i are the rows of the shard
+    (item_lo, item_stride, items.shape[0]): local row l is global item item_lo + l * item_stride; the ids of `pairs` are global.
+    A pair whose item the shard owns gets its (exact score, global id) key, -1 (all ones) when the score is NaN; every other
+    pair 0, so that an int64 sum over the shards is the complete key array (0: nobody owns the item)."""
+    n_local, d = items.shape
+    U, n_pairs, item_lo, item_stride = _rank_shard_args("rank_shard_keys", users_tab, user_ids, pairs, None, n_pairs, item_lo, item_stride)
+    out = torch.empty(n_pairs, dtype=torch.int64, device=items.device)
+    cv, cp = _c_args(c)
+    check(_lib.lib().macr_rank_shard_keys(kind, U, n_local, d, _ptr(users_tab, _f32), _ptr(user_ids, _i32, True), _ptr(items, _f32),
+                                          _ptr(sig_u, _f32, True), _ptr(sig_i, _f32, True), cv, cp, item_lo, item_stride,
+                                          _ptr(pairs.ptr, _i32), _ptr(pairs.idx, _i32), n_pairs, _ptr(out), _stream()))
+    return out
+
+
+def rank_shard_counts(kind, users_tab, user_ids, items, pairs, keys, sig_u=None, sig_i=None, c=0.0, mask=None, item_lo=0,
+                      item_stride=1, n_pairs=None):
+    """int64[n_pairs]: given the COMPLETE keys (rank_shard_keys summed over the shards), the number of this shard's items
+    that rank before each pair, minus the shard's own items of the query's `mask` (global ids) that do, plus
+    _lib.RANK_SHARD_MASKED where the shard owns the pair's item and the query masks it (macr_rank_shard_counts).  The sum
+    over the shards goes to rank_shard_combine."""
+    n_local, d = items.shape
+    U, n_pairs, item_lo, item_stride = _rank_shard_args("rank_shard_counts", users_tab, user_ids, pairs, mask, n_pairs, item_lo, item_stride)
+    if keys.dtype != torch.int64 or keys.numel() < n_pairs:
+        raise MacrError(_lib.E_INVALID, "rank_shard_counts: the keys are int64[%d]" % n_pairs)
+    L = _lib.lib()
+    out = torch.empty(n_pairs, dtype=torch.int64, device=items.device)
+    need = L.macr_rank_shard_workspace_bytes(U, n_pairs, n_local, d)
+    ws = _rank_workspace(need, items.device)
+    cv, cp = _c_args(c)
+    check(L.macr_rank_shard_counts(kind, U, n_local, d, _ptr(users_tab, _f32), _ptr(user_ids, _i32, True), _ptr(items, _f32),
+                                   _ptr(sig_u, _f32, True), _ptr(sig_i, _f32, True), cv, cp, item_lo, item_stride,
+                                   _ptr(mask.ptr, _i32) if mask is not None else None,
+                                   _ptr(mask.idx, _i32) if mask is not None else None,
+                                   _ptr(pairs.ptr, _i32), _ptr(keys), n_pairs, _ptr(out), _ptr(ws), ws.numel(), _stream()))
+    return out
+
+
+def rank_shard_combine(keys, summed):
+    """int32[n_pairs]: the positions from the complete keys and the shards' summed counts (macr_rank_shard_combine): -1 where
+    nobody owns the pair's item, its score is NaN or its owner found it masked; else the sum -- rank_positions' output on
+    the whole table."""
+    n_pairs = keys.numel()
+    if keys.dtype != torch.int64 or summed.dtype != torch.int64 or summed.numel() != n_pairs:
+        raise MacrError(_lib.E_INVALID, "rank_shard_combine: keys and summed counts are int64 arrays of one length")
+    out = torch.empty(n_pairs, dtype=_i32, device=keys.device)
+    check(_lib.lib().macr_rank_shard_combine(n_pairs, _ptr(keys), _ptr(summed), _ptr(out), _stream()))
+    return out
+
+
 def colmean(x, out=None):
     """out: optional float64 device or pinned host tensor of x.shape[1:]"""
     rows = x.shape[0]

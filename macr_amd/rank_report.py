@@ -1,7 +1,8 @@
 """AUC, MRR and rank percentiles of held-out items from their full-catalogue positions: the host half of
-`MACR_RANK_REPORT=1`.
+`MACR_RANK_REPORT=1` and of `MACR_SHARD_RANK_REPORT=1`.
 
-The positions come from the device (ops.rank_positions / Evaluator.rank_positions: for every ground-truth pair the number of
+The positions come from the device (ops.rank_positions / Evaluator.rank_positions, or over item shards
+Evaluator.rank_positions_sharded: for every ground-truth pair the number of
 the user's candidates ranked before it, -1 for a pair that has no position); everything here is float64 bookkeeping on
 n_pairs integers.  The reference carries an `auc_loger` list through both training loops (macr_mf/train.py:386,:459) that
 nothing fills; this is what it would have held.
@@ -83,3 +84,15 @@ def enabled():
     """MACR_RANK_REPORT=1 in the environment: every evaluation of the command lines also prints format_line"""
     import os
     return os.environ.get("MACR_RANK_REPORT", "") == "1"
+
+
+def shard_enabled():
+    """MACR_SHARD_RANK_REPORT=1 in the environment: the same line from Evaluator.rank_report_sharded, which also counts where
+    the items are sharded -- several ranks, --row_shard 1 -- and on one rank gives what enabled() gives"""
+    import os
+    return os.environ.get("MACR_SHARD_RANK_REPORT", "") == "1"
+
+
+def wanted():
+    """either switch: an evaluation prints the line, once"""
+    return enabled() or shard_enabled()

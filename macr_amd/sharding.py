@@ -59,6 +59,23 @@ def gather_topk(local_val, local_idx, group=None):
     return halves[..., 1].contiguous().view(torch.float32), halves[..., 0].contiguous()
 
 
+def sum_over_ranks(t, group=None):
+    """Element-wise SUM of an int64 tensor over the ranks, identical on every rank (one all-reduce of 8 bytes per element).
+    Integer addition wraps and commutes, so the result does not depend on the order in which the collective adds its
+    operands -- what the item-sharded position count (Evaluator.rank_positions_sharded) rests on: keys that are x + 0 + ...
+    + 0 (the top bit may be set: an all-ones key is -1) and counts that are integers."""
+    if t.dtype != torch.int64:
+        raise TypeError("sum_over_ranks: int64, got %s" % t.dtype)
+    if world()[1] == 1 and not force_collectives():
+        return t
+    if t.is_cuda and dist.get_backend(group) == "gloo":
+        # test rig only (several ranks sharing one GPU cannot use RCCL): gloo reduces host tensors
+        return sum_over_ranks(t.cpu(), group).to(t.device)
+    out = t.clone()
+    dist.all_reduce(out, op=dist.ReduceOp.SUM, group=group)
+    return out
+
+
 def max_over_ranks(x, device):
     """max of a python float over ranks (bench timing contract)."""
     rank, ws = world()

@@ -128,7 +128,8 @@ def main(sweep=False):
     main_rank = sharding.is_main()           # several ranks: replicas train, ONE prints / logs / writes (rank 0)
     if rank_report.enabled() and sharding.world()[1] > 1:
         raise SystemExit("MACR_RANK_REPORT=1 counts positions over a whole, replicated item table: it has no item-sharded "
-                         "form; unset MACR_RANK_REPORT or evaluate on one rank")
+                         "form; unset MACR_RANK_REPORT and set MACR_SHARD_RANK_REPORT=1 for the same line counted over the "
+                         "shards, or evaluate on one rank")
 
     def say(text, end='\n'):
         if main_rank:
@@ -253,11 +254,11 @@ def main(sweep=False):
                         c, ret['recall'][0], ret['recall'][-1], ret['hr'][0], ret['hr'][-1], ret['ndcg'][0],
                         ret['ndcg'][-1])
             ret['hr'][0] = best_hr
-            if sweep and (args.out == 1 or rank_report.enabled() or exposure.enabled()):    # the diagnostics of the chosen c only (no hit at any c: the last one)
+            if sweep and (args.out == 1 or rank_report.wanted() or exposure.enabled()):    # the diagnostics of the chosen c only (no hit at any c: the last one)
                 model.update_c(sess, c_values[-1] if best_c is None else best_c)
                 if args.out == 1:
                     item_diagnostic(sess, model, users_to_test, args.test)
-                if rank_report.enabled():
+                if rank_report.wanted():
                     rank_diagnostic(sess, model, users_to_test, args.test)
                 if exposure.enabled():
                     exposure_diagnostic(sess, model, users_to_test, args.test)

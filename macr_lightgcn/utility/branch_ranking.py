@@ -48,7 +48,7 @@ def test(sess, model, users_to_test, drop_flag=False, train_set_flag=0, method="
         ret = {k: np.asarray(v) for k, v in ret.items()}
     if _bt.args.out == 1:
         item_diagnostic(sess, model, users_to_test, method)
-    if rank_report.enabled():
+    if rank_report.wanted():
         rank_diagnostic(sess, model, users_to_test, method)
     if exposure.enabled():
         exposure_diagnostic(sess, model, users_to_test, method)
@@ -73,14 +73,16 @@ def _popularity_tables():
 def rank_diagnostic(sess, model, users_to_test, method):
     """MACR_RANK_REPORT=1: one line on where the held-out items stand in the FULL ranking test() scores with the same arguments
     (same score kind, the model's current c -- after a sweep the chosen one): AUC, reciprocal rank and rank percentile over
-    the whole catalogue, overall and per train-popularity group of --out 1 (macr_amd/rank_report.py).  The main rank prints."""
+    the whole catalogue, overall and per train-popularity group of --out 1 (macr_amd/rank_report.py).  MACR_SHARD_RANK_REPORT=1:
+    the same line counted over item shards -- every rank counts its items, the counts are added.  The main rank prints."""
     one_branch = method in _ITEM_BRANCH
     evaluator, uid = (_evaluator_for if one_branch else _bt._evaluator_for)(model, users_to_test)
     kind = ops.SCORE_RUBI if one_branch else _bt._METHODS[method]
     ua, ia = model.propagated()
-    rep = evaluator.rank_report(kind, ua, uid, ia.contiguous(), model.w, model.w_user, model.rubi_c,
-                                branch=_branch(model, method) if one_branch else None,
-                                group_of=_popularity_tables()["group_of"], n_groups=len(popularity.POINTS) + 1)
+    report = evaluator.rank_report_sharded if rank_report.shard_enabled() else evaluator.rank_report
+    rep = report(kind, ua, uid, ia.contiguous(), model.w, model.w_user, model.rubi_c,
+                 branch=_branch(model, method) if one_branch else None,
+                 group_of=_popularity_tables()["group_of"], n_groups=len(popularity.POINTS) + 1)
     if sharding.is_main():
         print(rank_report.format_line(rep))
 

@@ -70,7 +70,7 @@ def test(sess, model, test_users, batch_test_flag=False, model_type='o', valid_s
                                 model.w, model.w_user, model.rubi_c)
     if args.out == 1:
         item_diagnostic(sess, model, test_users, model_type, valid_set)
-    if rank_report.enabled():
+    if rank_report.wanted():
         rank_diagnostic(sess, model, test_users, model_type, valid_set)
     if exposure.enabled():
         exposure_diagnostic(sess, model, test_users, model_type, valid_set)
@@ -111,14 +111,17 @@ def item_diagnostic(sess, model, test_users, model_type='o', valid_set="test"):
 def rank_diagnostic(sess, model, test_users, model_type='o', valid_set="test"):
     """MACR_RANK_REPORT=1: one line on where the held-out items stand in the FULL ranking test() scores with the same arguments
     (same score kind, the model's current c) -- AUC, reciprocal rank and rank percentile over the whole catalogue, overall
-    and per train-popularity group of --out 1 (macr_amd/rank_report.py).  The main rank prints."""
+    and per train-popularity group of --out 1 (macr_amd/rank_report.py).  MACR_SHARD_RANK_REPORT=1: the same line counted
+    over item shards -- every rank counts its items (also under --row_shard 1), the counts are added.  The main rank prints."""
     from macr_amd import sharding
     evaluator, uid = _evaluator_for(model, test_users, valid_set)
     model.sync()
     if "groups" not in _n_test:
         _n_test["groups"] = _item_groups()
-    rep = evaluator.rank_report(_MODEL_TYPES[model_type], model.user_embedding, uid, model.item_embedding, model.w, model.w_user,
-                                model.rubi_c, group_of=_n_test["groups"], n_groups=len(rate))
+    users_tab, ids = (model.query_rows(uid), None) if getattr(model, "sharded", False) else (model.user_embedding, uid)
+    report = evaluator.rank_report_sharded if rank_report.shard_enabled() else evaluator.rank_report
+    rep = report(_MODEL_TYPES[model_type], users_tab, ids, model.item_embedding, model.w, model.w_user, model.rubi_c,
+                 group_of=_n_test["groups"], n_groups=len(rate))
     if sharding.is_main():
         print(rank_report.format_line(rep))
 
@@ -230,7 +233,8 @@ def main(sweep=False):
     main_rank = sharding.is_main()           # several ranks: replicas train, ONE prints / logs / writes (rank 0)
     if rank_report.enabled() and (args.row_shard == 1 or sharding.world()[1] > 1):
         raise SystemExit("MACR_RANK_REPORT=1 counts positions over a whole, replicated item table: it has no %s form; "
-                         "unset MACR_RANK_REPORT or evaluate on one rank" % ("--row_shard 1" if args.row_shard == 1 else "item-sharded"))
+                         "unset MACR_RANK_REPORT and set MACR_SHARD_RANK_REPORT=1 for the same line counted over the shards, or "
+                         "evaluate on one rank" % ("--row_shard 1" if args.row_shard == 1 else "item-sharded"))
 
     def say(text):
         if main_rank:
@@ -359,11 +363,11 @@ def main(sweep=False):
                 if ret['hit_ratio'][0] > best[0]:
                     best = (ret['hit_ratio'][0], ret['recall'][0], ret['precision'][0], ret['ndcg'][0], c)
             ret['hit_ratio'][0], ret['recall'][0], ret['precision'][0], ret['ndcg'][0] = best[:4]
-            if sweep and (args.out == 1 or rank_report.enabled() or exposure.enabled()):    # the diagnostics of the chosen c only (no hit at any c: the last one)
+            if sweep and (args.out == 1 or rank_report.wanted() or exposure.enabled()):    # the diagnostics of the chosen c only (no hit at any c: the last one)
                 model.update_c(sess, best[4] if best[0] > 0 else c_values[-1])
                 if args.out == 1:
                     item_diagnostic(sess, model, users_to_test, rubi_type, args.valid_set)
-                if rank_report.enabled():
+                if rank_report.wanted():
                     rank_diagnostic(sess, model, users_to_test, rubi_type, args.valid_set)
                 if exposure.enabled():
                     exposure_diagnostic(sess, model, users_to_test, rubi_type, args.valid_set)
