@@ -916,8 +916,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ADAM == 2 ?
     //     log(tx*ty) = log(N^2 * r),  f'(x) = -ex*r*(dy*ny),  g'(y) = ey*r*(dx*nx),   N = nx*ny,  r = 1/(dx*nx*dy*ny)
     // -- 4 transcendentals (2 exp, 1 rcp, 1 log).  It is the same real function; in fp32 it differs from EXACT where
     // the reference's subtraction 1-s loses bits, i.e. by ~6e-8*e^y relative on (1-s): a wave takes FAST only when
-    // every column of its tile has -20 <= p, -20 <= n <= 3 (a, b are in (0,1), so |x| <= |p|, |y| <= |n|): no
-    // overflow of the products, and EXACT/FAST agree to ~1e-6 relative per term, below the 1e-5 loss tolerance.
+    // every column of its tile has -20 <= p amax, YLO <= n bmax <= 6 over the wave's rows (kBxbYHi = 6; YLO = kBxbYLoSingle
+    // = -20 here, kBxbYLoPairs = -60 for run_tile_pairs; the test itself is below, at amax): no overflow of the products,
+    // and EXACT/FAST agree to 6e-6 relative per term at worst (y near 6), below the 1e-5 loss tolerance.
     auto run_tile = [&](auto fast_t) {
         constexpr bool FAST = decltype(fast_t)::value;
 #pragma unroll 2
@@ -1114,7 +1115,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ADAM == 2 ?
 #elif defined(MACR_ABL_BXB_FORCEFAST)
     const bool fast = true;
 #else
-    // The window of the 4-transcendental form is a statement about x = p*a and y = n*b: -20 <= x, YLO <= y <= 3.  a and b
+    // The window of the 4-transcendental form is a statement about x = p*a and y = n*b: -20 <= x, YLO <= y <= 6 (kBxbYHi).  a and b
     // are products of sigmoids, in (0,1) and usually well below 1, so the wave bounds them by the maxima over ITS rows:
     // x >= min(p,0)*amax, y <= max(n,0)*bmax, y >= min(n,0)*bmax.  (Columns alone -- a, b bounded by 1 -- put 40-60 % of
     // the tiles of a model a few hundred steps old on the exact side for the 1 % of its negatives that score above 3:

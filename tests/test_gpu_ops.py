@@ -198,8 +198,9 @@ def test_mf_trajectory_with_ieee_adam():
 @pytest.mark.parametrize("scale", [0.45, 0.6, 1.2])
 @pytest.mark.parametrize("B", [300, 4096])
 def test_mf_rubibceboth_large_logits(ops, scale, B):
-    """The (B,B) kernel takes its 4-transcendental form only for column tiles with -20 <= p, -20 <= n <= 3 and the
-    operation-by-operation form otherwise.  Larger embeddings put tiles on both sides of that test (scale 0.6: dot
+    """The (B,B) kernel takes its 4-transcendental form only for column tiles with -20 <= p amax and YLO <= n bmax <= 6 over
+    the wave's rows (YLO = -20 at B = 300, one row per lane; -60 at B = 4096, rows in pairs) and the operation-by-operation
+    form otherwise; tests/test_gpu_bxb_forms.py sits at those edges.  Larger embeddings put tiles on both sides of that test (scale 0.6: dot
     products of std ~3) or almost all on the exact side (1.2: std ~12, saturated sigmoids); loss and gradients must
     follow the oracle (which mirrors the reference's 1-sigmoid subtraction) everywhere."""
     d, n_users, n_items = 64, 5000, 900
