@@ -154,7 +154,14 @@ TEST_SIGNATURES = {
     "macr_test_bf16_scores_workspace_bytes": (_z, [_i, _i, _i]),
     "macr_test_bf16_scores": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _f, _p, _p, _p, _z, _p]),
     "macr_test_f16_scores": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _f, _p, _p, _p, _z, _p]),
+    "macr_test_radix_sort_workspace_bytes": (_z, [_i]),
+    "macr_test_radix_sort": (_i, [_i, _p, _p, ctypes.c_uint32, _p, _p, _p, _z, _p]),
+    "macr_test_sort_hist_words": (_z, [_i]),
+    "macr_test_sort_tile_for": (_i, [_i]),
+    "macr_test_ref_reduce_workspace_bytes": (_z, [_i, _i]),
+    "macr_test_ref_reduce": (_i, [_i] * 9 + [_p] * 3 + [_p] + [_p] * 4 + [_p] * 2 + [_p, _z, _p]),
 }
+TEST_REDUCE, TEST_INDEX, TEST_DET, TEST_INV = 0, 1, 2, 3       # MACR_TEST_* modes of macr_test_ref_reduce
 
 _lib = None
 _test = None

@@ -3302,6 +3302,36 @@ extern "C" int macr_shard_stage(int B, int d, float **stage, void *workspace, si
 /* this rank's rows: sort the references to them, one owner per row sums its staging rows, dense Adam over the shard
  * (lazy != NULL: the lazy pass -- the batch's rows and this step's K-th of the shard) */
 namespace macr {
+// The row sums behind shard_apply's sort, in the form the step asked for (inv, else det, else INDEX mode or the plain reduce):
+// gP/gQ and the row flags of this rank's rows from the sorted references r and the staging rows.  (A function of its own so that
+// the test-only macr_test_ref_reduce issues the very same launches.)
+static int shard_reduce(bool inv, bool det, bool indexed, int B, int d, int n_users_loc, int n_items_loc, const RefSort &r,
+                        float *gP, float *gQ, int32_t *touchedP, int32_t *touchedQ, const PairWs &ws, hipStream_t st) {
+    const int n = 3 * B;
+    if (inv) {
+        // as below, with chunks that begin at the run's start: the shape of a row's sum depends on its references alone
+        const uint32_t key_end = (uint32_t)(n_users_loc + n_items_loc);
+        MACR_DISPATCH_LPR(d, (k_seg_reduce_inv<LPR><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
+                                 n, n_users_loc, key_end, r.sk, r.sv, ws.stage, gP, gQ, touchedP, touchedQ, ws.cpart)));
+        MACR_CHECK_LAUNCH("seg_reduce_inv", st);
+        MACR_DISPATCH_LPR(d, (k_seg_fold_inv<LPR><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
+                                 n, n_users_loc, key_end, r.sk, ws.cpart, gP, gQ)));
+        MACR_CHECK_LAUNCH("seg_fold_inv", st);
+    } else if (det) {
+        // chunk sums of the cut runs to slots of their own, then ONE owner per row adds them in position order: no atomics, and
+        // no INDEX mode (whose long runs are summed by k_seg_sum with atomics) whatever MACR_SEG_UNFUSED says
+        const uint32_t key_end = (uint32_t)(n_users_loc + n_items_loc);
+        MACR_DISPATCH_LPR(d, (k_seg_reduce<LPR, true><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
+                                 n, n_users_loc, key_end, r.sk, r.sv, ws.stage, gP, gQ, touchedP, touchedQ, nullptr, nullptr, ws.cpart, nullptr)));
+        MACR_CHECK_LAUNCH("seg_reduce", st);
+        MACR_DISPATCH_LPR(d, (k_seg_fold<LPR><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
+                                 n, n_users_loc, key_end, r.sk, ws.cpart, gP, gQ, nullptr, nullptr)));
+        MACR_CHECK_LAUNCH("seg_fold", st);
+    } else if (int e = indexed ? launch_seg_index(B, d, n_users_loc, n_items_loc, r, false, gP, gQ, touchedP, touchedQ, ws, st)
+                        : launch_seg_reduce(B, d, n_users_loc, n_items_loc, r, gP, gQ, touchedP, touchedQ, nullptr, nullptr, ws, st))
+        return e;
+    return MACR_OK;
+}
 static int shard_apply(int loss_kind, int B, int d, int n_users_loc, int n_items_loc, int u_lo, int u_stride, int i_lo,
                        int i_stride, const int32_t *u, const int32_t *i, const int32_t *j, float *P, float *Q, float *w,
                        float *wu, float *mP, float *vP, float *mQ, float *vQ, float *mw, float *vw, float *mwu, float *vwu,
@@ -3329,28 +3359,7 @@ static int shard_apply(int loss_kind, int B, int d, int n_users_loc, int n_items
     // every row, as before (A/B measurements, tests).
     const char *unfused = getenv("MACR_SEG_UNFUSED");
     const bool indexed = !det && (size_t)n <= kRefMaxRefs && !(unfused && unfused[0] == '1');
-    if (inv) {
-        // as below, with chunks that begin at the run's start: the shape of a row's sum depends on its references alone
-        const uint32_t key_end = (uint32_t)(n_users_loc + n_items_loc);
-        MACR_DISPATCH_LPR(d, (k_seg_reduce_inv<LPR><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
-                                 n, n_users_loc, key_end, r.sk, r.sv, ws.stage, gP, gQ, touchedP, touchedQ, ws.cpart)));
-        MACR_CHECK_LAUNCH("seg_reduce_inv", st);
-        MACR_DISPATCH_LPR(d, (k_seg_fold_inv<LPR><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
-                                 n, n_users_loc, key_end, r.sk, ws.cpart, gP, gQ)));
-        MACR_CHECK_LAUNCH("seg_fold_inv", st);
-    } else if (det) {
-        // chunk sums of the cut runs to slots of their own, then ONE owner per row adds them in position order: no atomics, and
-        // no INDEX mode (whose long runs are summed by k_seg_sum with atomics) whatever MACR_SEG_UNFUSED says
-        const uint32_t key_end = (uint32_t)(n_users_loc + n_items_loc);
-        MACR_DISPATCH_LPR(d, (k_seg_reduce<LPR, true><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
-                                 n, n_users_loc, key_end, r.sk, r.sv, ws.stage, gP, gQ, touchedP, touchedQ, nullptr, nullptr, ws.cpart, nullptr)));
-        MACR_CHECK_LAUNCH("seg_reduce", st);
-        MACR_DISPATCH_LPR(d, (k_seg_fold<LPR><<<(n + 256 / LPR - 1) / (256 / LPR), 256, 0, st>>>(
-                                 n, n_users_loc, key_end, r.sk, ws.cpart, gP, gQ, nullptr, nullptr)));
-        MACR_CHECK_LAUNCH("seg_fold", st);
-    } else if (int e = indexed ? launch_seg_index(B, d, n_users_loc, n_items_loc, r, false, gP, gQ, touchedP, touchedQ, ws, st)
-                        : launch_seg_reduce(B, d, n_users_loc, n_items_loc, r, gP, gQ, touchedP, touchedQ, nullptr, nullptr, ws, st))
-        return e;
+    if (int e = shard_reduce(inv, det, indexed, B, d, n_users_loc, n_items_loc, r, gP, gQ, touchedP, touchedQ, ws, st)) return e;
     AdamArgs a;
     long long nb = 0;
     adam_args_begin(a, d, hp);
@@ -3781,3 +3790,122 @@ extern "C" int macr_lgcn_train_step(int loss_kind, int B, int d, int n_users, in
                                   plan_dev, plan_host, u, i, j, T, w, wu, mT, vT, mw, vw, mwu, vwu, adam_pow, hp, losses, flags,
                                   workspace, workspace_bytes, stream);
 }
+
+#ifdef MACR_TEST_ENTRY_POINTS       // libmacr_hip_test.so only (include/macr_hip_test.h)
+#include "../../include/macr_hip_test.h"
+
+extern "C" size_t macr_test_sort_hist_words(int n) { return n > 0 ? sort_hist_words(n) : 0; }
+extern "C" int macr_test_sort_tile_for(int n) { return n > 0 ? sort_tile_for(n) : 0; }
+
+namespace macr {
+struct TestSortWs { uint32_t *ka, *va, *kb, *vb, *ghist; size_t bytes; };
+static TestSortWs carve_test_sort_ws(void *base, int n) {
+    TestSortWs w;
+    char *p = static_cast<char *>(base);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { void *r = p ? p + off : nullptr; off += align_up(bytes, 256); return r; };
+    w.ka = static_cast<uint32_t *>(take((size_t)n * 4)); w.va = static_cast<uint32_t *>(take((size_t)n * 4));
+    w.kb = static_cast<uint32_t *>(take((size_t)n * 4)); w.vb = static_cast<uint32_t *>(take((size_t)n * 4));
+    w.ghist = static_cast<uint32_t *>(take(sort_hist_words(n) * 4));
+    w.bytes = off;
+    return w;
+}
+// the staged members of a PairWs and the deterministic chunk slots, nothing else: what the sort and the four reductions touch
+static PairWs carve_test_reduce_ws(void *base, int B, int d, const float *stage) {
+    PairWs w = {};
+    const size_t nsort = 3 * (size_t)B;
+    const int ch = d / 4 < 16 ? d / 4 : 16;                 // = CH of k_seg_reduce
+    char *p = static_cast<char *>(base);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { void *r = p ? p + off : nullptr; off += align_up(bytes, 256); return r; };
+    w.staged = true;
+    w.ska = static_cast<uint32_t *>(take(nsort * 4)); w.sva = static_cast<uint32_t *>(take(nsort * 4));
+    w.skb = static_cast<uint32_t *>(take(nsort * 4)); w.svb = static_cast<uint32_t *>(take(nsort * 4));
+    w.ghist = static_cast<uint32_t *>(take(sort_hist_words((int)nsort) * 4));
+    w.n_work = static_cast<uint32_t *>(take(4));
+    w.cpart = static_cast<float *>(take(2 * ((nsort + ch - 1) / ch) * d * 4));      // (as carve_pair_ws_det sizes it)
+    w.stage = const_cast<float *>(stage);                   // the caller's rows: every reduction only reads them
+    w.bytes = off;
+    return w;
+}
+}  // namespace macr
+
+extern "C" size_t macr_test_radix_sort_workspace_bytes(int n) {
+    return n > 0 ? carve_test_sort_ws(nullptr, n).bytes : 0;
+}
+
+extern "C" int macr_test_radix_sort(int n, const uint32_t *keys, const uint32_t *vals, uint32_t max_key, uint32_t *keys_out,
+                                    uint32_t *vals_out, void *workspace, size_t workspace_bytes, void *stream) {
+    MACR_REQUIRE(n > 0 && keys && vals && keys_out && vals_out, MACR_E_INVALID, "test_radix_sort: bad argument");
+    MACR_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0, MACR_E_INVALID, "test_radix_sort: workspace");
+    const TestSortWs w = carve_test_sort_ws(workspace, n);
+    MACR_REQUIRE(workspace_bytes >= w.bytes, MACR_E_WORKSPACE, "test_radix_sort: workspace %zu < %zu bytes", workspace_bytes, w.bytes);
+    hipStream_t st = as_stream(stream);
+    const size_t nb = (size_t)n * 4;
+    if (hipMemcpyAsync(w.ka, keys, nb, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(w.va, vals, nb, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        macr::set_error("test_radix_sort: copy in");
+        return MACR_E_LAUNCH;
+    }
+    const int flip = launch_radix_sort(w.ka, w.va, w.kb, w.vb, n, max_key, w.ghist, st);
+    MACR_CHECK_LAUNCH("test_radix_sort", st);
+    if (hipMemcpyAsync(keys_out, flip ? w.kb : w.ka, nb, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(vals_out, flip ? w.vb : w.va, nb, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        macr::set_error("test_radix_sort: copy out");
+        return MACR_E_LAUNCH;
+    }
+    return MACR_OK;
+}
+
+extern "C" size_t macr_test_ref_reduce_workspace_bytes(int B, int d) {
+    if (B <= 0 || !dim_supported(d)) return 0;
+    return carve_test_reduce_ws(nullptr, B, d, nullptr).bytes;
+}
+
+extern "C" int macr_test_ref_reduce(int mode, int B, int d, int n_users_loc, int n_items_loc, int u_lo, int u_stride, int i_lo,
+                                    int i_stride, const int32_t *u, const int32_t *i, const int32_t *j, const float *stage,
+                                    float *gU, float *gI, int32_t *tU, int32_t *tI, uint32_t *sk_out, uint32_t *sv_out,
+                                    void *workspace, size_t workspace_bytes, void *stream) {
+    MACR_REQUIRE(mode >= MACR_TEST_REDUCE && mode <= MACR_TEST_INV, MACR_E_INVALID, "test_ref_reduce: mode=%d", mode);
+    MACR_REQUIRE(B > 0 && dim_supported(d), B > 0 ? MACR_E_UNSUPPORTED : MACR_E_INVALID, "test_ref_reduce: B=%d d=%d", B, d);
+    MACR_REQUIRE((size_t)3 * B <= kRefMaxRefs, MACR_E_UNSUPPORTED, "test_ref_reduce: B=%d", B);
+    MACR_REQUIRE(n_users_loc >= 0 && n_items_loc >= 0 && u_lo >= 0 && i_lo >= 0 && u_stride >= 1 && i_stride >= 1 && u && i && j &&
+                     stage && sk_out && sv_out && ((gU && tU) || n_users_loc == 0) && ((gI && tI) || n_items_loc == 0),
+                 MACR_E_INVALID, "test_ref_reduce: bad argument");
+    MACR_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0, MACR_E_INVALID, "test_ref_reduce: workspace");
+    PairWs ws = carve_test_reduce_ws(workspace, B, d, stage);
+    MACR_REQUIRE(workspace_bytes >= ws.bytes, MACR_E_WORKSPACE, "test_ref_reduce: workspace %zu < %zu bytes", workspace_bytes, ws.bytes);
+    hipStream_t st = as_stream(stream);
+    const int n = 3 * B;
+    const bool whole = u_lo == 0 && u_stride == 1 && i_lo == 0 && i_stride == 1 && mode != MACR_TEST_INV;
+    const uint32_t *sk = nullptr, *sv = nullptr;
+    if (whole) {
+        // the single-GPU step's sequence: k_refs_init + sort, then the reduction launch_ref_sort_reduce picks from the workspace
+        // (cpart: the deterministic pair) and from sv_sorted (INDEX mode)
+        MACR_REQUIRE(n_users_loc + n_items_loc > 0, MACR_E_INVALID, "test_ref_reduce: no rows");
+        if (mode != MACR_TEST_DET) ws.cpart = nullptr;
+        PairCall c;
+        c.B = B; c.d = d; c.n_urows = n_users_loc; c.n_irows = n_items_loc;
+        c.u = u; c.i = i; c.j = j; c.gU = gU; c.gI = gI; c.tU = tU; c.tI = tI;
+        c.sk_sorted = &sk;
+        if (int e = launch_ref_sort_reduce(c, mode == MACR_TEST_INDEX ? &sv : nullptr, nullptr, ws, st)) return e;
+        if (!sv) sv = sk == ws.ska ? ws.sva : ws.svb;
+    } else {
+        // the row-sharded step's sequence (shard_apply): k_shard_keys + sort, then shard_reduce
+        const Owned ou = {u_lo, u_stride, n_users_loc}, oi = {i_lo, i_stride, n_items_loc};
+        k_shard_keys<<<grid_for(B), 256, 0, st>>>(B, ou, oi, u, i, j, ws.ska, ws.sva, ws.n_work, nullptr, nullptr);
+        const RefSort r = ref_sort_result(ws, launch_radix_sort(ws.ska, ws.sva, ws.skb, ws.svb, n, (uint32_t)(n_users_loc + n_items_loc), ws.ghist, st));
+        MACR_CHECK_LAUNCH("ref_sort", st);
+        if (int e = shard_reduce(mode == MACR_TEST_INV, mode == MACR_TEST_DET || mode == MACR_TEST_INV, mode == MACR_TEST_INDEX, B, d,
+                                 n_users_loc, n_items_loc, r, gU, gI, tU, tI, ws, st))
+            return e;
+        sk = r.sk; sv = r.sv;
+    }
+    if (hipMemcpyAsync(sk_out, sk, (size_t)n * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(sv_out, sv, (size_t)n * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        macr::set_error("test_ref_reduce: copy out");
+        return MACR_E_LAUNCH;
+    }
+    return MACR_OK;
+}
+#endif  // MACR_TEST_ENTRY_POINTS

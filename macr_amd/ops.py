@@ -273,6 +273,59 @@ def test_f16_scores(kind, users, items, sig_u=None, sig_i=None, c=0.0):
     return out, margin
 
 
+def test_sort_hist_words(n):
+    """TEST-ONLY (host): words of tile counts + digit totals a sort of up to n pairs may need (refsort.hpp::sort_hist_words)"""
+    return int(_lib.test_lib().macr_test_sort_hist_words(int(n)))
+
+
+def test_sort_tile_for(n):
+    """TEST-ONLY (host): keys per workgroup of a sort of n pairs (refsort.hpp::sort_tile_for, MACR_SORT_TILE included)"""
+    return int(_lib.test_lib().macr_test_sort_tile_for(int(n)))
+
+
+def _as_u32(t):
+    """int32 storage read as uint32 words (torch has no arithmetic on uint32: the tests carry keys as int32 bit patterns)"""
+    if t.dtype != _i32:
+        raise TypeError("expected int32 storage, got %s" % t.dtype)
+    return _ptr(t)
+
+
+def test_radix_sort(keys, vals, max_key):
+    """TEST-ONLY (macr_test_radix_sort): launch_radix_sort on (keys, vals) -- int32 tensors holding uint32 bit patterns --
+    with one pass per 8 bits of max_key -> (sorted keys, their values), same storage."""
+    n = keys.numel()
+    L = _lib.test_lib()
+    ws = torch.empty(L.macr_test_radix_sort_workspace_bytes(n), dtype=torch.uint8, device=keys.device)
+    ko, vo = torch.empty_like(keys), torch.empty_like(vals)
+    _check_test(L.macr_test_radix_sort(n, _as_u32(keys), _as_u32(vals), int(max_key), _as_u32(ko), _as_u32(vo), _ptr(ws),
+                                       ws.numel(), _stream()))
+    return ko, vo
+
+
+def test_ref_reduce_workspace(B, d, device):
+    """TEST-ONLY: the scratch of test_ref_reduce (callers keep it to call twice on the same workspace)"""
+    return torch.empty(_lib.test_lib().macr_test_ref_reduce_workspace_bytes(B, d), dtype=torch.uint8, device=device)
+
+
+def test_ref_reduce(mode, u, i, j, stage, owned, gU, gI, tU, tI, ws):
+    """TEST-ONLY (macr_test_ref_reduce): keys of the batch's 3B references, the sort, and the row reduction `mode`
+    (_lib.TEST_REDUCE / TEST_INDEX / TEST_DET / TEST_INV) of the staging rows stage[3B][d] into the caller's gU/gI (fp32 rows)
+    and tU/tI (int32 flags; None for a table without rows).  owned = (u_lo, u_stride, n_users_loc, i_lo, i_stride, n_items_loc).
+    -> (sorted keys, sorted values) as int32 storage."""
+    _require_f32(stage=stage)
+    B, d = u.numel(), stage.shape[1]
+    if stage.shape[0] != 3 * B:
+        raise ValueError("stage must have 3B rows")
+    u_lo, u_stride, n_users_loc, i_lo, i_stride, n_items_loc = (int(x) for x in owned)
+    sk = torch.empty(3 * B, dtype=_i32, device=u.device)
+    sv = torch.empty(3 * B, dtype=_i32, device=u.device)
+    L = _lib.test_lib()
+    _check_test(L.macr_test_ref_reduce(int(mode), B, d, n_users_loc, n_items_loc, u_lo, u_stride, i_lo, i_stride, _ptr(u, _i32),
+                                       _ptr(i, _i32), _ptr(j, _i32), _ptr(stage, _f32), _ptr(gU, _f32, True), _ptr(gI, _f32, True),
+                                       _ptr(tU, _i32, True), _ptr(tI, _i32, True), _ptr(sk), _ptr(sv), _ptr(ws), ws.numel(), _stream()))
+    return sk, sv
+
+
 SEED_WIDTH = 32          # MACR_SEED_WIDTH
 _topk_ws_cache = {}
 
