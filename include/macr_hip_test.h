@@ -6,7 +6,8 @@
  *   - the raw products and scores of the bf16 / fp16 candidate filters with the error margin the filter grants them (the
  *     reference has no counterpart: it scores in fp32, macr_mf/model.py:199);
  *   - the staged gradient path of the training steps: the radix sort of the row references (refsort.hpp) and the four row
- *     reductions behind it, on caller-chosen keys and staging rows. */
+ *     reductions behind it, on caller-chosen keys and staging rows;
+ *   - where the MF step's workspace holds the outputs of pair_fwd. */
 #ifndef MACR_HIP_TEST_H
 #define MACR_HIP_TEST_H
 #include "macr_hip.h"
@@ -74,6 +75,12 @@ int macr_test_ref_reduce(int mode, int B, int d, int n_users_loc, int n_items_lo
                          int i_stride, const int32_t *u, const int32_t *i, const int32_t *j, const float *stage,
                          float *gU, float *gI, int32_t *tU, int32_t *tI, uint32_t *sk_out, uint32_t *sv_out,
                          void *workspace, size_t workspace_bytes, void *stream);
+
+/* TEST-ONLY, host only: where the MF training step keeps pair_fwd's outputs in its workspace.  fwd_offset_bytes: the distance
+ * from the workspace's first byte to `fwd`, seven arrays of *Bp floats (p, n, a, b, sig_si, sig_sj, and sig_su or the BPR
+ * cell's factor, whose sign bit is the column flag of the BCE kinds); entry t < B of array k is float k * *Bp + t.
+ * deterministic != 0: the layout of a step that carries MACR_STEP_DETERMINISTIC. */
+int macr_test_pair_ws_layout(int B, int d, int deterministic, size_t *fwd_offset_bytes, int *Bp);
 
 #ifdef __cplusplus
 }

@@ -158,6 +158,7 @@ TEST_SIGNATURES = {
     "macr_test_radix_sort": (_i, [_i, _p, _p, ctypes.c_uint32, _p, _p, _p, _z, _p]),
     "macr_test_sort_hist_words": (_z, [_i]),
     "macr_test_sort_tile_for": (_i, [_i]),
+    "macr_test_pair_ws_layout": (_i, [_i, _i, _i, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]),
     "macr_test_ref_reduce_workspace_bytes": (_z, [_i, _i]),
     "macr_test_ref_reduce": (_i, [_i] * 9 + [_p] * 3 + [_p] + [_p] * 4 + [_p] * 2 + [_p, _z, _p]),
 }

@@ -534,8 +534,10 @@ struct PendingAdam {
 // PENDING (deferred mode): the previous step's Adam update has not been applied yet -- it is applied to ALL rows
 // by the Adam blocks riding in this step's bxb launch.  The forward needs the updated rows now, so every lane
 // computes theta' = adam(theta, m, v, g) for the float4 it gathers (and for w, w_user) in registers, with exactly
-// the arithmetic the pass will use, and writes nothing back: 3x more bytes gathered per row, no atomics, no
-// ordering between references to the same row, no extra launch.
+// the arithmetic the pass will use -- adam4, and for w and w_user the pass's association of the kBranchSlots partial
+// rows, which depends on LPR (below) -- and writes nothing back: 3x more bytes gathered per row, no atomics, no
+// ordering between references to the same row, no extra launch.  (tests/test_gpu_deferred_forms.py holds the forward's
+// outputs and the riding pass's stores to the stand-alone pass bit for bit.)
 // PENDING = 2: the tables are updated lazily (adam_lazy_scan_block) -- a gathered row may be several steps behind: its idle
 // steps first (stamp + 1 .. pending step - 1, in registers), then the pending step as above.  The lane group also marks
 // its three rows (flag bit 1) so that the pass riding in this step's (B,B) launch brings them to the pending step IN
@@ -582,11 +584,29 @@ __global__ __launch_bounds__(256) void k_pair_fwd(
             // gradient rows are read unconditionally: rows without a gradient are all-zero (the scratch invariant),
             // and a flag test would put a second memory latency in front of the row load
             const float4 gu = ld4(pa.gU + au), gi = ld4(pa.gI + ai), gj = ld4(pa.gI + aj);
+            // the partial rows of the branch vectors, in the ASSOCIATION of the pass (adam_block<PARTS>): its 256 / LPR lane
+            // groups sum rows grp, grp + ngrp, ... each, then the group sums are added in group order.  With a row or none
+            // per group (LPR <= 32) that is the rows one after another; at LPR = 64 four groups hold two rows each
             float4 gw4 = make_float4(0, 0, 0, 0), gwu4 = make_float4(0, 0, 0, 0);
+            if constexpr (256 / LPR >= kBranchSlots) {
 #pragma unroll
-            for (int k = 0; k < kBranchSlots; ++k) {
-                gw4 = add4(gw4, ld4(gw + (size_t)k * 2 * d + 4 * g.sub));
-                gwu4 = add4(gwu4, ld4(gw + (size_t)k * 2 * d + d + 4 * g.sub));
+                for (int k = 0; k < kBranchSlots; ++k) {
+                    gw4 = add4(gw4, ld4(gw + (size_t)k * 2 * d + 4 * g.sub));
+                    gwu4 = add4(gwu4, ld4(gw + (size_t)k * 2 * d + d + 4 * g.sub));
+                }
+            } else {
+                constexpr int kGroups = 256 / LPR;
+#pragma unroll
+                for (int grp = 0; grp < kGroups; ++grp) {
+                    float4 sw = make_float4(0, 0, 0, 0), swu = make_float4(0, 0, 0, 0);
+#pragma unroll
+                    for (int k = grp; k < kBranchSlots; k += kGroups) {
+                        sw = add4(sw, ld4(gw + (size_t)k * 2 * d + 4 * g.sub));
+                        swu = add4(swu, ld4(gw + (size_t)k * 2 * d + d + 4 * g.sub));
+                    }
+                    gw4 = add4(gw4, sw);
+                    gwu4 = add4(gwu4, swu);
+                }
             }
             float4 mw4 = ld4(pa.mw + 4 * g.sub), vw4 = ld4(pa.vw + 4 * g.sub);
             float4 mwu4 = ld4(pa.mwu + 4 * g.sub), vwu4 = ld4(pa.vwu + 4 * g.sub);
@@ -3796,6 +3816,18 @@ extern "C" int macr_lgcn_train_step(int loss_kind, int B, int d, int n_users, in
 
 extern "C" size_t macr_test_sort_hist_words(int n) { return n > 0 ? sort_hist_words(n) : 0; }
 extern "C" int macr_test_sort_tile_for(int n) { return n > 0 ? sort_tile_for(n) : 0; }
+
+extern "C" int macr_test_pair_ws_layout(int B, int d, int deterministic, size_t *fwd_offset_bytes, int *Bp) {
+    MACR_REQUIRE(B > 0 && fwd_offset_bytes && Bp, MACR_E_INVALID, "test_pair_ws_layout: bad argument");
+    MACR_REQUIRE(dim_supported(d), MACR_E_UNSUPPORTED, "test_pair_ws_layout: d=%d not in {32,64,128,256}", d);
+    // carved on a base that is never dereferenced: only the distances are read
+    const uintptr_t base = 4096;
+    const PairWs ws = deterministic ? carve_pair_ws_det(reinterpret_cast<void *>(base), B, d)
+                                    : carve_pair_ws(reinterpret_cast<void *>(base), B, d);
+    *fwd_offset_bytes = (size_t)(reinterpret_cast<uintptr_t>(ws.fwd) - base);
+    *Bp = ws.Bp;
+    return MACR_OK;
+}
 
 namespace macr {
 struct TestSortWs { uint32_t *ka, *va, *kb, *vb, *ghist; size_t bytes; };

@@ -283,6 +283,14 @@ def test_sort_tile_for(n):
     return int(_lib.test_lib().macr_test_sort_tile_for(int(n)))
 
 
+def test_pair_ws_layout(B, d, deterministic):
+    """TEST-ONLY (host): where an MF training step of B triples keeps pair_fwd's outputs in its workspace -> (byte offset of
+    `fwd`, Bp): seven arrays of Bp floats, entry t < B of array k at float k * Bp + t (include/macr_hip_test.h)"""
+    off, Bp = ctypes.c_size_t(0), ctypes.c_int(0)
+    _check_test(_lib.test_lib().macr_test_pair_ws_layout(int(B), int(d), int(bool(deterministic)), ctypes.byref(off), ctypes.byref(Bp)))
+    return int(off.value), int(Bp.value)
+
+
 def _as_u32(t):
     """int32 storage read as uint32 words (torch has no arithmetic on uint32: the tests carry keys as int32 bit patterns)"""
     if t.dtype != _i32:

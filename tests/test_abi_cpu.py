@@ -37,9 +37,9 @@ def test_test_only_entry_points_live_in_their_own_library(lib):
     src = open(os.path.join(REPO, "include", "macr_hip_test.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     declared = sorted(set(re.findall(r"\b(macr_[a-z0-9_]+)\s*\(", src)))
-    assert declared == sorted(_lib.TEST_SIGNATURES) and len(declared) == 11
+    assert declared == sorted(_lib.TEST_SIGNATURES) and len(declared) == 12
     assert {"macr_test_radix_sort", "macr_test_radix_sort_workspace_bytes", "macr_test_sort_hist_words", "macr_test_sort_tile_for",
-            "macr_test_ref_reduce", "macr_test_ref_reduce_workspace_bytes"} <= set(declared)
+            "macr_test_ref_reduce", "macr_test_ref_reduce_workspace_bytes", "macr_test_pair_ws_layout"} <= set(declared)
     T = _lib.test_lib()
     for name in declared:
         assert hasattr(T, name), name
