@@ -435,6 +435,7 @@ extern "C" int macr_rank_positions(int score_kind, int U, int n_local, int d, co
     // blocks of 8 waves resident on 256 CUs; never more than the work has tiles (an upper bound: the columns are counted
     // on the device)
     const long long w_max = ((long long)(std::min<long long>(U, n_pairs) + n_pairs / kColPairs) / kRankCols + 1) * T;
+    // (restated as geometry() of tests/rank_cases.py: its cases are placed by this arithmetic)
     const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(d <= 64 ? 512 : 256, w_max));
     MACR_RANK_DISPATCH_DK(d, score_kind, {
         auto count = k_rank_count<D, KIND, false>;
@@ -512,6 +513,7 @@ extern "C" int macr_rank_shard_counts(int score_kind, int U, int n_local, int d,
     const unsigned pblocks = (unsigned)((n_pairs + 255) / 256);
     const int T = (n_local + kRankTile - 1) / kRankTile;
     const long long w_max = ((long long)(std::min<long long>(U, n_pairs) + n_pairs / kColPairs) / kRankCols + 1) * T;      // as macr_rank_positions
+    // (restated as geometry() of tests/rank_cases.py: its cases are placed by this arithmetic)
     const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(d <= 64 ? 512 : 256, w_max));
     MACR_RANK_DISPATCH_DK(d, score_kind, {
         auto count = k_rank_count<D, KIND, true>;
