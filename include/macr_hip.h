@@ -956,6 +956,35 @@ int macr_item_exposure(int U, int K, int k, const int32_t *rankings, const int32
                        void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Two top-k rankings of the same queries compared list by list (additive, abi 16): what a second ranking ("here": the
+ * corrected one) replaced of a first ("base": the factual one), how high up, and what that did to the hits -- the device
+ * half of MACR_SHIFT_REPORT (macr_amd/shift_report.py).  The reference has no such read-out.
+ *   rank_base (dev) int32[U*K_base], rank_here (dev) int32[U*K_here]: per query the ranked ids outside its train list, best
+ *             first, -1 in unused slots, no id twice in a row (what macr_score_topk / macr_topk_merge leave without the
+ *             -inf fill); only the first k slots of a row are read.  A VALID id is 0 <= id < n_items; any other slot is
+ *             skipped, as macr_item_counts skips it.
+ *   gt_ptr / gt_idx (dev) the ground truth as CSR, ascending per query, as macr_metrics_mf takes it (its binary search)
+ *   per_user  (dev, 16-byte aligned) int32[U*8] <- per query
+ *             {n_base, n_here    valid entries of each row,
+ *              common            entries of here whose id occurs in base,
+ *              first_diff        smallest p < k with base[p] != here[p] (raw slots, -1 included); k if there is none,
+ *              footrule          sum over the common ids of |position in base - position in here|,
+ *              hits_base, hits_here, hits_common   entries of base / here / the common ones whose id is in the ground truth}
+ *   entered   (dev) int32[U*k] <- per query the valid ids of here that are not in base, in ASCENDING ID order, then -1
+ *   left      (dev) int32[U*k] <- the same for the ids of base that are not in here
+ *             (ascending: the non-negative entries, read row-major, are a pair_item array of macr_rank_positions, and either
+ *             array is a `rankings` of macr_item_counts with K = k)
+ * One launch, no workspace, no atomics, integers only; every output element is stored once (the caller need not zero them).
+ * Form: one wave per query, four queries per workgroup, both rows in LDS; membership, the position in the
+ * other row and the ascending output slot (the number of smaller entered / left ids) by k broadcast LDS reads per entry.
+ * Refused before any device work with MACR_E_INVALID: U < 1, k < 1, k > K_base or k > K_here, a stride above MACR_MAX_TOPK,
+ * n_items <= 0, a null pointer, a per_user that is not 16-byte aligned.
+ * -------------------------------------------------------------------------*/
+int macr_list_shift(int U, int K_base, int K_here, int k, const int32_t *rank_base, const int32_t *rank_here,
+                    const int32_t *gt_ptr, const int32_t *gt_idx, int n_items,
+                    int32_t *per_user, int32_t *entered, int32_t *left, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Scores and full-catalogue positions of given (query, item) pairs (additive, abi 16).  The reference's test()
  * (macr_mf/train.py:224-251) materialises the whole (U, N) score matrix and ranklist_by_sorted keeps its first K columns;
  * these two calls answer for ANY pair -- a held-out item at position 900 as well as one at position 3 -- what that

@@ -207,9 +207,134 @@ __global__ __launch_bounds__(256) void k_exposure_finish(int n_items, const ulon
     if (group_out && threadIdx.x < 2 * n_groups && sums[threadIdx.x]) atomicAdd(&group_out[threadIdx.x], sums[threadIdx.x]);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Two rankings of the same queries, list by list (macr_list_shift, MACR_SHIFT_REPORT): what the second ("here") replaced
+// of the first ("base"), how high up, and what that did to the hits.  One wave per query, kShiftQueries queries per
+// workgroup; both rows' first k slots sit in LDS (k <= MACR_MAX_TOPK = 128: one or two entries per lane).  An entry finds
+// its id in the other row by k broadcast LDS reads; an id that is valid and absent there has entered (here) or left
+// (base), and its output slot in ascending id order is the number of smaller entered (left) ids, counted by k more
+// broadcast reads -- no sort.  The eight per-query integers are popcounts of 64-bit ballots and one wave sum, written by
+// lane 0 as one 32-byte row.  Every output element of a query is stored exactly once: no atomics, nothing to zero.
+constexpr int kShiftQueries = 4;
+constexpr int kShiftAbsent = 0x7fffffff;             // in the entered / left scratch rows: not an entered / left id
+static_assert(MACR_MAX_TOPK == 2 * kWave, "a lane holds at most two entries of a row");
+
+__device__ __forceinline__ int shift_wave_sum(int v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, kWave);
+    return v;
+}
+
+__global__ __launch_bounds__(kShiftQueries * kWave) void k_list_shift(int U, int K_base, int K_here, int k, int n_items,
+                                                                     const int32_t *__restrict__ rank_base,
+                                                                     const int32_t *__restrict__ rank_here,
+                                                                     const int32_t *__restrict__ gt_ptr, const int32_t *__restrict__ gt_idx,
+                                                                     int32_t *__restrict__ per_user, int32_t *__restrict__ entered,
+                                                                     int32_t *__restrict__ left) {
+    __shared__ int32_t rows[kShiftQueries][4][MACR_MAX_TOPK];        // base, here, left ids, entered ids: 8 KB
+    const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+    const long long u = (long long)blockIdx.x * kShiftQueries + wave;
+    const bool live = u < U;                          // (a wave past the last query still meets the barriers)
+    int32_t *sb = rows[wave][0], *sh = rows[wave][1], *sl = rows[wave][2], *se = rows[wave][3];
+    int32_t idb[2], idh[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int p = lane + j * kWave;
+        idb[j] = idh[j] = -1;
+        if (live && p < k) {
+            idb[j] = rank_base[(size_t)u * K_base + p];
+            idh[j] = rank_here[(size_t)u * K_here + p];
+            sb[p] = idb[j];
+            sh[p] = idh[j];
+        }
+    }
+    __syncthreads();
+    const int a = live ? gt_ptr[u] : 0, n_gt = live ? gt_ptr[u + 1] - a : 0;
+    int n_base = 0, n_here = 0, common = 0, first_diff = k, footrule = 0, hits_base = 0, hits_here = 0, hits_common = 0;
+    bool is_left[2] = {false, false}, is_entered[2] = {false, false};
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        if (j * kWave >= k) break;                    // (uniform: k <= 64 has no second entry in any lane)
+        const int p = lane + j * kWave;
+        const bool mine = live && p < k;
+        const bool vb = mine && idb[j] >= 0 && idb[j] < n_items, vh = mine && idh[j] >= 0 && idh[j] < n_items;
+        int at_base = -1, at_here = -1;               // where the here id stands in base, the base id in here
+        for (int q = 0; q < k; ++q) {                 // (rows without repeated ids: at most one slot matches)
+            if (vh && sb[q] == idh[j]) at_base = q;
+            if (vb && sh[q] == idb[j]) at_here = q;
+        }
+        const bool kept = at_base >= 0;
+        const bool hit_b = vb && item_in_sorted(gt_idx + a, n_gt, idb[j]);
+        const bool hit_h = vh && item_in_sorted(gt_idx + a, n_gt, idh[j]);
+        is_left[j] = vb && at_here < 0;
+        is_entered[j] = vh && !kept;
+        if (mine) {
+            sl[p] = is_left[j] ? idb[j] : kShiftAbsent;
+            se[p] = is_entered[j] ? idh[j] : kShiftAbsent;
+        }
+        n_base += __popcll(__ballot(vb));
+        n_here += __popcll(__ballot(vh));
+        common += __popcll(__ballot(kept));
+        hits_base += __popcll(__ballot(hit_b));
+        hits_here += __popcll(__ballot(hit_h));
+        hits_common += __popcll(__ballot(hit_h && kept));
+        footrule += kept ? (at_base > p ? at_base - p : p - at_base) : 0;
+        const unsigned long long differ = __ballot(mine && idb[j] != idh[j]);       // raw slots, -1 included
+        if (differ && first_diff == k) first_diff = j * kWave + __ffsll((long long)differ) - 1;
+    }
+    footrule = shift_wave_sum(footrule);
+    __syncthreads();
+    int total_left = 0, total_entered = 0;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        total_left += __popcll(__ballot(is_left[j]));
+        total_entered += __popcll(__ballot(is_entered[j]));
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int p = lane + j * kWave;
+        if (!live || p >= k) continue;
+        // ascending slot = the smaller ids of the same list (an equal id further left counts too: a row that repeats an
+        // id against the contract still fills every slot once)
+        int below_l = 0, below_e = 0;
+        for (int q = 0; q < k; ++q) {
+            const int32_t xl = sl[q], xe = se[q];
+            below_l += (xl < idb[j] || (xl == idb[j] && q < p)) ? 1 : 0;
+            below_e += (xe < idh[j] || (xe == idh[j] && q < p)) ? 1 : 0;
+        }
+        if (is_left[j]) left[(size_t)u * k + below_l] = idb[j];
+        if (is_entered[j]) entered[(size_t)u * k + below_e] = idh[j];
+        if (p >= total_left) left[(size_t)u * k + p] = -1;
+        if (p >= total_entered) entered[(size_t)u * k + p] = -1;
+    }
+    if (live && lane == 0) {
+        int4 *out = reinterpret_cast<int4 *>(per_user + (size_t)u * 8);
+        out[0] = make_int4(n_base, n_here, common, first_diff);
+        out[1] = make_int4(footrule, hits_base, hits_here, hits_common);
+    }
+}
+
 }  // namespace macr
 
 using namespace macr;
+
+extern "C" int macr_list_shift(int U, int K_base, int K_here, int k, const int32_t *rank_base, const int32_t *rank_here,
+                               const int32_t *gt_ptr, const int32_t *gt_idx, int n_items, int32_t *per_user, int32_t *entered,
+                               int32_t *left, void *stream) {
+    hipStream_t st = as_stream(stream);
+    MACR_REQUIRE(U >= 1 && k >= 1, MACR_E_INVALID, "list_shift: U=%d k=%d", U, k);
+    MACR_REQUIRE(k <= K_base && k <= K_here, MACR_E_INVALID, "list_shift: k=%d above a row stride (K_base=%d, K_here=%d)", k, K_base, K_here);
+    MACR_REQUIRE(K_base <= MACR_MAX_TOPK && K_here <= MACR_MAX_TOPK, MACR_E_INVALID,
+                 "list_shift: K_base=%d K_here=%d above MACR_MAX_TOPK=%d", K_base, K_here, MACR_MAX_TOPK);
+    MACR_REQUIRE(n_items > 0, MACR_E_INVALID, "list_shift: n_items=%d", n_items);
+    MACR_REQUIRE(rank_base && rank_here && gt_ptr && gt_idx && per_user && entered && left, MACR_E_INVALID, "list_shift: null pointer");
+    MACR_REQUIRE((reinterpret_cast<uintptr_t>(per_user) & 15) == 0, MACR_E_INVALID, "list_shift: per_user is not 16-byte aligned");
+    const unsigned blocks = (unsigned)(((long long)U + kShiftQueries - 1) / kShiftQueries);
+    k_list_shift<<<blocks, kShiftQueries * kWave, 0, st>>>(U, K_base, K_here, k, n_items, rank_base, rank_here, gt_ptr, gt_idx,
+                                                           per_user, entered, left);
+    MACR_CHECK_LAUNCH("list_shift", st);
+    return MACR_OK;
+}
 
 extern "C" size_t macr_item_counts_workspace_bytes(int U, int K, int n_items) {
     if (U <= 0 || K < 1 || n_items <= 0) return 0;

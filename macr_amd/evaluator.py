@@ -99,6 +99,8 @@ class Evaluator(object):
         # the same for a STRIDED shard (set_local_items): local row l is item lo + l * stride
         self._local_own = None
         self._mask_lists = mask_lists
+        self._gt_lists = gt_lists
+        self._base = None                         # (shard it was built for, the evaluator list_shift ranks the base with)
 
     def set_local_items(self, own):
         """`items_tab` is this rank's shard of an item table sharded like the training state (sharded_train.Owned: local
@@ -307,21 +309,81 @@ class Evaluator(object):
         exp_w, hit_w, sums = ops.item_exposure(idx, self.gt, exposure.position_weights(k), self.n_items, group_of, n_groups or 0)
         return rec, exp_w, hit_w, sums
 
+    # ------------------------------------------------------------------ list shift report (MACR_SHIFT_REPORT)
+    def _base_evaluator(self):
+        """The evaluator list_shift ranks the base with: the same lists and item shard as this one, seeds, policy counters and
+        graph cache of its own -- a second ranking of another score kind leaves this evaluator's state as it was."""
+        shard = (self._local_own, None if self.local_items_range is None else tuple(self.local_items_range))
+        if self._base is None or self._base[0] != shard:
+            ev = Evaluator(self._mask_lists, self._gt_lists, self.n_items, self.device)
+            if self._local_own is not None:
+                ev.set_local_items(self._local_own)
+            elif self.local_items_range is not None:
+                ev.local_items_range = tuple(self.local_items_range)
+            self._base = (shard, ev)
+        return self._base[1]
+
+    def list_shift(self, kind, users_tab, user_ids, items_tab, k, w=None, wu=None, c=0.0, branch=None,
+                   base_kind=ops.SCORE_NORMAL, base_c=0.0, group_of=None, n_groups=None):
+        """What the correction changed, query by query: the top-k ranking an evaluation with the same arguments scores
+        ("here") against the top-k ranking by base_kind / base_c ("base", default: the factual ranking --test normal prints).
+        -> (per_user, entered, left, entered_counts, left_counts) on the device: int32 (U,8) {n_base, n_here, common,
+        first_diff, footrule, hits_base, hits_here, hits_common} and int32 (U,k) the ids that entered / left each list,
+        ascending, then -1 (ops.list_shift), and ops.item_counts of the entered and of the left lists: (rec_cnt, hit_cnt,
+        group_sums) -- how often an item entered (left) a list, how often as a gained (lost) hit, and with group_of (n_items
+        group ids, 0 .. n_groups-1; n_groups None: max + 1) the int64 (n_groups, 2) sums per group, else None.
+        Both are ranked as item_exposure ranks (rank() without the -inf fill, `here` at the evaluator's last depth when that
+        is deeper than k) and compared on the MERGED rankings, which every rank holds after rank()'s all-gather: correct under
+        item sharding (several ranks, set_local_items) without a collective of its own.  The base is ranked by an evaluator
+        of its own (_base_evaluator)."""
+        k = int(k)
+        depth = max(k, getattr(self, "_last_depth", 0))
+        _, here, _ = self.rank(kind, users_tab, user_ids, items_tab, depth, w, wu, c, fill_masked=False, branch=branch)
+        _, base, _ = self._base_evaluator().rank(base_kind, users_tab, user_ids, items_tab, k, w, wu, base_c, fill_masked=False,
+                                                 branch=branch)
+        per_user, entered, left = ops.list_shift(base, here, self.gt, k, self.n_items)
+        group_of, n_groups = self._groups_on_device(group_of, n_groups)
+        counts = tuple(ops.item_counts(ids, self.gt, k, self.n_items, group_of, n_groups or 0) for ids in (entered, left))
+        return per_user, entered, left, counts[0], counts[1]
+
+    @staticmethod
+    def _pairs_of(ids):
+        """(ptr, idx, n_pairs): the non-negative entries of an (U,k) id array, row by row, as the pair CSR of rank_positions"""
+        valid = ids >= 0
+        ptr = torch.zeros(ids.shape[0] + 1, dtype=torch.int32, device=ids.device)
+        ptr[1:] = torch.cumsum(valid.sum(dim=1), 0)
+        idx = ids[valid].contiguous()
+        n_pairs = int(idx.numel())
+        return ptr, (idx if n_pairs else torch.zeros(1, dtype=torch.int32, device=ids.device)), n_pairs
+
+    def shift_depth(self, kind, users_tab, user_ids, items_tab, entered, left, w=None, wu=None, c=0.0, branch=None,
+                    base_kind=ops.SCORE_NORMAL, base_c=0.0):
+        """(pos_entered, pos_left): int32 on the device, one per non-negative entry of list_shift's `entered` / `left` read
+        row-major -- the exact 0-based position of every entered item in the full BASE ranking (how deep the correction
+        reached for it) and of every left item in the full ranking by kind / c (how far it fell); -1 as rank_positions
+        gives it.  A whole, replicated item table on one rank only (rank_positions' NotImplementedError otherwise)."""
+        pos_entered = self.rank_positions(base_kind, users_tab, user_ids, items_tab, w, wu, base_c, branch, pairs=self._pairs_of(entered))
+        pos_left = self.rank_positions(kind, users_tab, user_ids, items_tab, w, wu, c, branch, pairs=self._pairs_of(left))
+        return pos_entered, pos_left
+
     # ------------------------------------------------------------------ full-catalogue positions (MACR_RANK_REPORT=1)
-    def rank_positions(self, kind, users_tab, user_ids, items_tab, w=None, wu=None, c=0.0, branch=None):
+    def rank_positions(self, kind, users_tab, user_ids, items_tab, w=None, wu=None, c=0.0, branch=None, pairs=None):
         """int32[n_gt] on the device, in the order of the ground-truth CSR: for every held-out (query, item) pair the number
         of the query's candidates -- the catalogue minus its train items -- ranked before the item by the score an
         evaluation with the same arguments ranks by (score descending, ties by ascending id): the index rank() would
         give the item with K large enough, wherever it stands.  -1: the item is also a train item of the query, or scores
         NaN.  The branch factors are computed as rank() computes them (branch: the ego item rows of LightGCN's rubi2).
-        One item shard only (NotImplementedError otherwise): rank_positions_sharded adds the counts of several shards."""
+        One item shard only (NotImplementedError otherwise): rank_positions_sharded adds the counts of several shards.
+        pairs: optional (ptr, idx, n_pairs) CSR over the queries, device int32, ascending per query, in place of the ground
+        truth -- int32[n_pairs] in its order (shift_depth: the items that entered or left a list)."""
         if sharding.world()[1] > 1 or self._local_own is not None or self.local_items_range is not None:
             raise NotImplementedError("Evaluator.rank_positions ranks a whole, replicated item table: item-sharded "
                                       "evaluation (several ranks, set_local_items) has no position count yet")
         if items_tab.shape[0] != self.n_items:
             raise _lib.MacrError(_lib.E_INVALID, "rank_positions: %d item rows for an evaluator of %d items" % (items_tab.shape[0], self.n_items))
         sig_u, sig_i = self._branch_factors(kind, users_tab, user_ids, items_tab if branch is None else branch, w, wu)
-        return ops.rank_positions(kind, users_tab, user_ids, items_tab, self.gt, sig_u, sig_i, c, self.mask, n_pairs=self.n_gt)
+        csr, n_pairs = (self.gt, self.n_gt) if pairs is None else (ops.CSR(pairs[0], pairs[1]), int(pairs[2]))
+        return ops.rank_positions(kind, users_tab, user_ids, items_tab, csr, sig_u, sig_i, c, self.mask, n_pairs=n_pairs)
 
     @staticmethod
     def _branch_factors(kind, users_tab, user_ids, branch_tab, w, wu):

@@ -624,6 +624,26 @@ def item_exposure(rankings, gt, weights, n_items, group_of=None, n_groups=0):
     return exp_w, hit_w, sums
 
 
+def list_shift(rank_base, rank_here, gt, k, n_items, out=None):
+    """Two (U,K) rankings of the same queries (-1 = unused slot; the strides may differ) + ground-truth CSR ->
+    (per_user, entered, left) by macr_list_shift, over the first k slots of each row: int32 (U,8) {n_base, n_here, common,
+    first_diff, footrule, hits_base, hits_here, hits_common}, and int32 (U,k) the valid ids of rank_here that are not in
+    rank_base / of rank_base that are not in rank_here, ascending, then -1.  Exact integers, every element overwritten.
+    out: optional (per_user, entered, left) tensors to write into."""
+    U, K_base = rank_base.shape
+    if rank_here.dim() != 2 or rank_here.shape[0] != U or gt.ptr.numel() != U + 1:
+        raise MacrError(_lib.E_INVALID, "list_shift: two rankings and a ground-truth CSR of the same %d queries expected" % U)
+    k, dev = int(k), rank_base.device
+    if out is None:
+        out = (torch.empty((U, 8), dtype=_i32, device=dev), torch.empty((U, max(k, 0)), dtype=_i32, device=dev),
+               torch.empty((U, max(k, 0)), dtype=_i32, device=dev))
+    per_user, entered, left = out
+    check(_lib.lib().macr_list_shift(U, K_base, rank_here.shape[1], k, _ptr(rank_base, _i32), _ptr(rank_here, _i32),
+                                     _ptr(gt.ptr, _i32), _ptr(gt.idx, _i32), int(n_items), _ptr(per_user, _i32),
+                                     _ptr(entered, _i32), _ptr(left, _i32), _stream()))
+    return per_user, entered, left
+
+
 def score_pairs(kind, users_tab, user_ids, items, pairs, sig_u=None, sig_i=None, c=0.0, n_pairs=None):
     """fp32[n_pairs]: the score of every (query, item) pair of the CSR `pairs` over the queries (macr_score_pairs) -- bit for
     bit what score_matrix holds at [q, item]; NaN for an item outside the table.  n_pairs: pairs.ptr[-1] where the caller

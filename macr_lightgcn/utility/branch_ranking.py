@@ -10,7 +10,7 @@ import torch
 
 from utility import batch_test as _bt
 
-from macr_amd import exposure, ops, popularity, rank_report, sharding
+from macr_amd import exposure, ops, popularity, rank_report, sharding, shift_report
 from macr_amd.eval_cache import EvaluatorCache
 from macr_amd.evaluator import Evaluator
 
@@ -52,6 +52,8 @@ def test(sess, model, users_to_test, drop_flag=False, train_set_flag=0, method="
         rank_diagnostic(sess, model, users_to_test, method)
     if exposure.enabled():
         exposure_diagnostic(sess, model, users_to_test, method)
+    if shift_report.enabled() and method != "normal":
+        shift_diagnostic(sess, model, users_to_test, method)
     return ret
 
 
@@ -104,6 +106,30 @@ def exposure_diagnostic(sess, model, users_to_test, method):
     if sharding.is_main():
         print(exposure.format_line(exposure.summarize(rec.cpu().numpy(), exp_w.cpu().numpy(), hit_w.cpu().numpy(),
                                                       tables["train_counts"], tables["group_of"], n_groups, len(users_to_test), k)))
+
+
+def shift_diagnostic(sess, model, users_to_test, method):
+    """MACR_SHIFT_REPORT=1: one line on what the correction changed, user by user -- the top-max(Ks) lists test() ranks with the
+    same arguments (same score kind, the model's current c -- after a sweep the chosen one) against the lists of the factual
+    ranking (--test normal): how much of the lists was replaced and how high up, the hits kept, gained and lost on the same
+    users with the exact sign test, and the train-popularity groups the replaced slots went to and came from
+    (macr_amd/shift_report.py).  =2 adds the full-catalogue depth of the items that entered and left.  Every rank ranks; the
+    main rank prints."""
+    one_branch = method in _ITEM_BRANCH
+    evaluator, uid = (_evaluator_for if one_branch else _bt._evaluator_for)(model, users_to_test)
+    kind = ops.SCORE_RUBI if one_branch else _bt._METHODS[method]
+    group_of = _popularity_tables()["group_of"]
+    k, n_groups = max(model.Ks), len(popularity.POINTS) + 1
+    ua, ia = model.propagated()
+    tables, branch = (kind, ua, uid, ia.contiguous()), _branch(model, method) if one_branch else None
+    per_user, entered, left, (e_rec, e_hit, _), (l_rec, l_hit, _) = evaluator.list_shift(
+        *tables, k, model.w, model.w_user, model.rubi_c, branch=branch, group_of=group_of, n_groups=n_groups)
+    depth = None
+    if shift_report.enabled() == 2:
+        depth = [p.cpu().numpy() for p in evaluator.shift_depth(*tables, entered, left, model.w, model.w_user, model.rubi_c, branch=branch)]
+    if sharding.is_main():
+        print(shift_report.format_line(shift_report.summarize(per_user.cpu().numpy(), e_rec.cpu().numpy(), e_hit.cpu().numpy(),
+                                                              l_rec.cpu().numpy(), l_hit.cpu().numpy(), group_of, n_groups, k, depth)))
 
 
 def item_diagnostic(sess, model, users_to_test, method):

@@ -24,7 +24,7 @@ import torch
 from batch_test import *          # noqa: F401,F403  (args, data, Ks, BATCH_SIZE, ITEM_NUM, USER_NUM)
 from model import BPRMF, Session
 
-from macr_amd import exposure, ops, popularity, rank_report
+from macr_amd import exposure, ops, popularity, rank_report, shift_report
 from macr_amd.evaluator import Evaluator
 from macr_amd.eval_cache import EvaluatorCache
 from macr_amd.metrics_host import (precision_at_k, dcg_at_k, ndcg_at_k, recall_at_k, hit_at_k,   # noqa: F401
@@ -74,6 +74,8 @@ def test(sess, model, test_users, batch_test_flag=False, model_type='o', valid_s
         rank_diagnostic(sess, model, test_users, model_type, valid_set)
     if exposure.enabled():
         exposure_diagnostic(sess, model, test_users, model_type, valid_set)
+    if shift_report.enabled() and _MODEL_TYPES[model_type] != ops.SCORE_NORMAL:
+        shift_diagnostic(sess, model, test_users, model_type, valid_set)
     return ret
 
 
@@ -146,6 +148,33 @@ def exposure_diagnostic(sess, model, test_users, model_type='o', valid_set="test
     if sharding.is_main():
         print(exposure.format_line(exposure.summarize(rec.cpu().numpy(), exp_w.cpu().numpy(), hit_w.cpu().numpy(), counts,
                                                       group_of, n_groups, len(test_users), k)))
+
+
+def shift_diagnostic(sess, model, test_users, model_type='rubi_both', valid_set="test"):
+    """MACR_SHIFT_REPORT=1: one line on what the correction changed, user by user -- the top-max(Ks) lists test() ranks with the
+    same arguments (same score kind, the model's current c) against the lists of the factual ranking (--test normal): how much
+    of the lists was replaced and how high up, the hits kept, gained and lost on the same users with the exact sign test,
+    and the train-popularity groups the replaced slots went to and came from (macr_amd/shift_report.py).  =2 adds the
+    full-catalogue depth of the items that entered and left.  Compared on the merged rankings: every rank ranks (also under
+    --row_shard 1), the main rank prints."""
+    from macr_amd import sharding
+    evaluator, uid = _evaluator_for(model, test_users, valid_set)
+    model.sync()
+    if "exposure" not in _n_test:
+        counts = popularity.train_counts(data.train_item_list, ITEM_NUM)
+        _n_test["exposure"] = (counts, popularity.item_groups(counts))
+    group_of = _n_test["exposure"][1]
+    k, n_groups = max(Ks), len(popularity.POINTS) + 1
+    users_tab, ids = (model.query_rows(uid), None) if getattr(model, "sharded", False) else (model.user_embedding, uid)
+    tables = (_MODEL_TYPES[model_type], users_tab, ids, model.item_embedding)
+    per_user, entered, left, (e_rec, e_hit, _), (l_rec, l_hit, _) = evaluator.list_shift(
+        *tables, k, model.w, model.w_user, model.rubi_c, group_of=group_of, n_groups=n_groups)
+    depth = None
+    if shift_report.enabled() == 2:
+        depth = [p.cpu().numpy() for p in evaluator.shift_depth(*tables, entered, left, model.w, model.w_user, model.rubi_c)]
+    if sharding.is_main():
+        print(shift_report.format_line(shift_report.summarize(per_user.cpu().numpy(), e_rec.cpu().numpy(), e_hit.cpu().numpy(),
+                                                              l_rec.cpu().numpy(), l_hit.cpu().numpy(), group_of, n_groups, k, depth)))
 
 
 def test_sweep(sess, model, test_users, cs, model_type='rubi_both', valid_set="test"):
@@ -235,6 +264,10 @@ def main(sweep=False):
         raise SystemExit("MACR_RANK_REPORT=1 counts positions over a whole, replicated item table: it has no %s form; "
                          "unset MACR_RANK_REPORT and set MACR_SHARD_RANK_REPORT=1 for the same line counted over the shards, or "
                          "evaluate on one rank" % ("--row_shard 1" if args.row_shard == 1 else "item-sharded"))
+    if shift_report.enabled() == 2 and (args.row_shard == 1 or sharding.world()[1] > 1):
+        raise SystemExit(shift_report.refusal("--row_shard 1" if args.row_shard == 1 else "item-sharded"))
+    if shift_report.enabled() and args.test != "rubi" and main_rank:
+        print(shift_report.NOTHING_TO_COMPARE)
 
     def say(text):
         if main_rank:
@@ -363,7 +396,7 @@ def main(sweep=False):
                 if ret['hit_ratio'][0] > best[0]:
                     best = (ret['hit_ratio'][0], ret['recall'][0], ret['precision'][0], ret['ndcg'][0], c)
             ret['hit_ratio'][0], ret['recall'][0], ret['precision'][0], ret['ndcg'][0] = best[:4]
-            if sweep and (args.out == 1 or rank_report.wanted() or exposure.enabled()):    # the diagnostics of the chosen c only (no hit at any c: the last one)
+            if sweep and (args.out == 1 or rank_report.wanted() or exposure.enabled() or shift_report.enabled()):    # the diagnostics of the chosen c only (no hit at any c: the last one)
                 model.update_c(sess, best[4] if best[0] > 0 else c_values[-1])
                 if args.out == 1:
                     item_diagnostic(sess, model, users_to_test, rubi_type, args.valid_set)
@@ -371,6 +404,8 @@ def main(sweep=False):
                     rank_diagnostic(sess, model, users_to_test, rubi_type, args.valid_set)
                 if exposure.enabled():
                     exposure_diagnostic(sess, model, users_to_test, rubi_type, args.valid_set)
+                if shift_report.enabled():
+                    shift_diagnostic(sess, model, users_to_test, rubi_type, args.valid_set)
                 model.update_c(sess, c_values[-1])   # (what the loop left, and what a checkpoint records)
             if best[0] > config['best_c_hr']:
                 config['best_c_hr'], config['best_c'], config['best_c_epoch'] = best[0], best[4], epoch
