@@ -114,6 +114,27 @@ def isolated():
     return _cache["isolated"]
 
 
+STAR_SHAPE = (640, 40)
+STAR_HUB = 520
+
+
+def star():
+    """640 users x 40 items, N = 680: item 0 is linked to users 0..519 -- 520 entries, just above the 512 at which a plan
+    splits a row -- and every user to one random other item.  Small enough for FOUR exact layers (exact_case: 520^3 weights
+    of at most 3 stay below 2^24 granules; a fifth layer cannot with a hub this long)."""
+    if "star" not in _cache:
+        n_users, n_items = STAR_SHAPE
+        rs = np.random.RandomState(3)
+        rows = np.concatenate([np.arange(STAR_HUB), np.arange(n_users)])
+        cols = np.concatenate([np.zeros(STAR_HUB, np.int64), 1 + rs.randint(0, n_items - 1, n_users)])
+        R = sp.coo_matrix((np.ones(len(rows), np.float32), (rows, cols)), shape=STAR_SHAPE).tocsr()
+        assert R.nnz == len(rows)
+        A = sp.bmat([[None, R], [R.T, None]]).tocsr().astype(np.float32)
+        A.sort_indices()
+        _cache["star"] = A
+    return _cache["star"]
+
+
 # ----------------------------------------------------------------------------- plans
 def build_plan_host(A, lib):
     """the plan of CSR matrix A as macr_spmm_plan_build writes it (int32 array), under the environment of the moment"""
@@ -307,6 +328,58 @@ def lgcn_counts(ops, state):
         wf = max(wf, _lib.lib().macr_lgcn_work_floats(N, d, state.adj_t._plan_ptrs()[1]))
     off = 3 * up(N * d * 4) + up(wf * 4)
     return state.ws[off:off + 4 * N].view(_torch().int32)
+
+
+def lgcn_scratch_regions(ops, state):
+    """{name: tensor view} of every region of a default-mode LGCNState's workspace that train_kernels.hip carve_lgcn_ws (and
+    launch_propagate for the inside of `work`) calls zero between steps:
+        dE        (N, d) floats behind E: the gradient w.r.t. the propagated table (the fused epilogue clears the batch's rows,
+                  the dense route clears all of it on return)
+        cnt       N int32: references of the current batch per row (= lgcn_counts)
+        emb_acc   2048 doubles (kEmbSlots): emb_loss partial sums, read and cleared by k_lgcn_finalize
+        sbr       N floats: --loss bce2's branch scalar per ego row
+        arrivals  int32 arrival counters of the hub groups and rows of the adjacency's plan: inside `work`, behind the
+                  4 N d floats of the layer buffers and the slab rows (pieces + groups of whichever schedule of the plan has
+                  more), to the end of macr_lgcn_work_floats; `arrivals_t` the same of adj_t's plan.  Absent without a plan.
+    gw, the kBranchSlots partial rows of the branch-vector gradients, is NOT among them.  adam_block (k_lgcn_finalize /
+    k_adam_dense) stores zeros over the partial rows of a segment it consumes, but only the segments of the step's kind
+    exist: under bce1 / bce2 pair_bwd still adds a w_user half into every row (sums of dsu e_u, which vanish only because
+    sig(su) = 1 makes dsu = 0 in its arithmetic) and nothing clears it.  The step does not rely on gw being clean either:
+    block 0 of k_pair_fwd clears all of it before the step's pair_bwd adds."""
+    from macr_amd import _lib
+    torch = _torch()
+    N, d = state.T.shape
+    up = lambda n: (n + 255) // 256 * 256
+    nd = up(N * d * 4)
+    plans = [state.adj] + ([state.adj_t] if state.adj_t is not None else [])
+    wf = max(_lib.lib().macr_lgcn_work_floats(N, d, a._plan_ptrs()[1]) for a in plans)
+    ws = state.ws
+    out = {"dE": ws[nd:nd + N * d * 4].view(torch.float32)}
+    work = ws[3 * nd:3 * nd + wf * 4]
+    for key, a in zip(("arrivals", "arrivals_t"), plans):
+        if a.plan_host is None:
+            continue
+        P = decode_plan(a.plan_host)
+        S = P["stream"] or P
+        slab_rows = max(P["n_slots"] + P["n_groups"], S["n_slots"] + S["n_groups"])
+        n_cnt = max(P["n_groups"] + P["n_split"], S["n_groups"] + S["n_split"]) + 64
+        lo = (4 * N * d + slab_rows * d) * 4
+        assert lo + n_cnt * 4 == _lib.lib().macr_lgcn_work_floats(N, d, a._plan_ptrs()[1]) * 4 <= work.numel()
+        out[key] = work[lo:lo + n_cnt * 4].view(torch.int32)
+    off = 3 * nd + up(wf * 4)
+    out["cnt"] = ws[off:off + 4 * N].view(torch.int32)
+    off += up(4 * N)
+    out["emb_acc"] = ws[off:off + 2048 * 8].view(torch.float64)
+    off += 2048 * 8
+    out["sbr"] = ws[off:off + 4 * N].view(torch.float32)
+    return out
+
+
+def assert_scratch_clean(ops, state, what):
+    """every region of lgcn_scratch_regions holds zeros (a NaN counts as dirt)"""
+    for name, region in lgcn_scratch_regions(ops, state).items():
+        dirty = int((region != 0).sum())
+        assert dirty == 0, "%s: %d non-zero entries left in %s" % (what, dirty, name)
 
 
 def _torch():

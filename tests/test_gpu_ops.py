@@ -514,7 +514,7 @@ def toy_graph(n_users, n_items, seed, density=0.1):
 
 
 @pytest.mark.parametrize("d", [32, 64, 128, 256])
-@pytest.mark.parametrize("L", [0, 1, 2, 3])
+@pytest.mark.parametrize("L", [0, 1, 2, 3, 4, 5])
 def test_lgcn_propagate_matches_oracle(ops, d, L):
     n_users, n_items = 700, 333
     A = toy_graph(n_users, n_items, 3)

@@ -41,7 +41,7 @@ def ops():
 
 
 _cases, _adj = {}, {}
-GRAPHS = {"small": sc.small, "deep": sc.deep, "isolated": sc.isolated}
+GRAPHS = {"small": sc.small, "deep": sc.deep, "isolated": sc.isolated, "star": sc.star}
 
 
 def exact(graph, d, L):
@@ -97,15 +97,26 @@ def test_rows_without_neighbours_outnumber_the_stream_chunks(ops, d, L):
     run_settings(ops, "isolated", d, L, ["plan", "noplan", "stream"])
 
 
+@pytest.mark.parametrize("L", [3, 4])
+@pytest.mark.parametrize("d", [32, 64, 128, 256])
+def test_hub_rows_propagate_exactly_star(ops, d, L):
+    """STAR: one hub row of 520 entries (two pieces in slot order, eight under the default cuts, nine or sixteen of 64), small
+    enough to stay exact through FOUR layers -- the first at which launch_propagate writes a layer into a buffer pair [X | S]
+    that an earlier layer wrote (layer 2 reuses pair 0, layer 3 pair 1; three layers never overwrite one)."""
+    run_settings(ops, "star", d, L, ["plan", "octants0", "noplan", "stream", "chunk64"])
+
+
 # ----------------------------------------------------------------------------- b. real weights
+@pytest.mark.parametrize("L", [3, 4, 5])
 @pytest.mark.parametrize("d", [32, 64])
-def test_hub_rows_real_weights_three_layers(ops, d):
-    """D^-1/2 A D^-1/2 on SMALL, L = 3 (not exact: guards the rounding path) against a float64 product.  Element-wise bound
+def test_hub_rows_real_weights_three_layers(ops, d, L):
+    """D^-1/2 A D^-1/2 on SMALL, L = 3 and the depths at which layer buffers are reused, 4 and 5 (not exact: guards the rounding
+    path) against a float64 product.  Element-wise bound
     L gamma M + 4 u M, u = 2^-24, M = the float64 mean over the layers of |A|^l |E0|, gamma = (chunk + 2 kGroup + number of
     groups of the longest row) u: the first-order worst case of the kernel's summation tree (an fma chain of at most `chunk`
     entries, kGroup partials per group, the groups in rounds of kGroup) per layer, plus the L running-sum additions and the
     final scaling.  Derived, not measured."""
-    L, u = 3, 2.0 ** -24
+    u = 2.0 ** -24
     A = sc.sym_norm(sc.small())
     rs = np.random.RandomState(5 + d)
     E0 = rs.standard_normal((A.shape[0], d)).astype(np.float32)
@@ -129,7 +140,7 @@ def test_hub_rows_real_weights_three_layers(ops, d):
         out = torch.full(E0.shape, float("nan"), dtype=torch.float32, device="cuda")
         got = ops.lgcn_propagate(adj, sc.dev(E0), L, out=out).cpu().numpy().astype(np.float64)
         err = np.abs(got - want)
-        print("%s d=%d: max err / bound = %.3g" % (setting, d, (err / np.maximum(bound, 1e-300)).max()))
+        print("%s d=%d L=%d: max err / bound = %.3g" % (setting, d, L, (err / np.maximum(bound, 1e-300)).max()))
         assert np.all(err <= bound), (setting, float((err / np.maximum(bound, 1e-300)).max()))
 
 

@@ -16,7 +16,7 @@ SETTINGS = {
     "stream_hub32_t32": {"MACR_SPMM_STREAM": "1", "MACR_SPMM_HUB": "32", "MACR_SPMM_T": "32"},
     "stream_octants0": {"MACR_SPMM_STREAM": "1", "MACR_SPMM_OCTANTS": "0"},
 }
-GRAPHS = {"small": sc.small, "deep": sc.deep, "sparse": sc.sparse_graph, "isolated": sc.isolated}
+GRAPHS = {"small": sc.small, "deep": sc.deep, "sparse": sc.sparse_graph, "isolated": sc.isolated, "star": sc.star}
 
 
 @pytest.fixture(scope="module")
@@ -300,3 +300,12 @@ def test_graphs_keep_their_group_count_edges(lib, monkeypatch):
     S = sc.decode_plan(plan_of(lib, monkeypatch, "deep", "stream"))["stream"]
     assert sc.groups_per_row(S)[n_u + 0] > 2 * sc.K_GROUP and sc.groups_per_row(S)[n_u + 1] > sc.K_GROUP
     assert S["n_groups"] == 113
+    # STAR (exact at four layers): ONE hub row of 520 entries, just past the split threshold -- two pieces in slot order, eight
+    # short ones cut at the source ranges (the default), nine / sixteen of at most 64 entries; always a single group
+    n_u = sc.STAR_SHAPE[0]
+    assert sc.star().shape[0] == 680 and int(deg(sc.star())[n_u]) == sc.STAR_HUB > 512 > int(deg(sc.star())[n_u + 1:].max())
+    for setting, pieces in (("octants0", 2), ("defaults", 8), ("chunk64_octants0", 9), ("chunk64", 16)):
+        P = sc.decode_plan(plan_of(lib, monkeypatch, "star", setting))
+        assert sc.group_sizes(P) == [pieces] and sc.groups_per_row(P) == {n_u: 1}, setting
+    S = sc.decode_plan(plan_of(lib, monkeypatch, "star", "stream"))["stream"]
+    assert sc.group_sizes(S) == [8] and sc.groups_per_row(S) == {n_u: 1}
