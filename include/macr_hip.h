@@ -985,6 +985,37 @@ int macr_list_shift(int U, int K_base, int K_here, int k, const int32_t *rank_ba
                     int32_t *per_user, int32_t *entered, int32_t *left, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Per row, a histogram of item groups and a weighted sum (additive, abi 16): the popularity mix of every user's list and of
+ * every user's profile -- the device half of MACR_CALIBRATION_REPORT (macr_amd/calibration.py).  The reference has no such
+ * read-out.  Two forms of rows:
+ *   ranking form, row_ptr == NULL: row u is ids[u*stride + p], p < k, 1 <= k <= stride; the slots past k are not read
+ *             (what macr_score_topk / macr_topk_merge leave without the -inf fill)
+ *   CSR form, row_ptr (dev) int32[U+1] given: row u is ids[row_ptr[u] .. row_ptr[u+1]); stride and k must both be 0
+ *             (the evaluator's mask CSR, which holds the train lists; a row may be empty or thousands of entries long)
+ * A VALID entry has 0 <= id < n_items; any other slot (-1, 2^31 - 1) is skipped, as macr_item_counts skips it.
+ *   gt_ptr / gt_idx (dev) the ground truth as CSR, ascending per row, as macr_metrics_mf takes it (its binary search);
+ *             hit, gt_ptr and gt_idx are all given or all NULL
+ *   group_of  (dev) int32[n_items] the group of every item; 1 <= n_groups <= 64
+ *   item_weight (dev) int32[n_items] or NULL
+ *   cnt  (dev) int32[U*n_groups] <- cnt[u*n_groups + g] = valid entries of row u with group_of[id] == g; a valid id whose
+ *             group lies outside [0, n_groups) is in no column
+ *   hit  (dev) int32[U*n_groups] <- the same count over the entries whose id is in ground-truth row u
+ *   wsum (dev, 16-byte aligned) long long[U*2] or NULL <- {sum of item_weight[id] over the valid entries of the row (exact
+ *             64-bit sum; 0 without item_weight), number of valid entries whatever their group}
+ * One launch, no workspace, no global atomics, integers only; every output element is stored exactly once (the caller need
+ * not zero them); the same bytes from run to run.
+ * Form: one wave per row, four rows per workgroup; the wave walks its row in chunks of 64 entries, one
+ * gather from group_of (and item_weight) per lane, the wave's own 64 LDS counters, one wave sum for the weights.
+ * Refused before any device work with MACR_E_INVALID: U < 1, n_items <= 0, n_groups outside [1, 64], a null ids, group_of
+ * or cnt, ranking form with k < 1 or k > stride, CSR form with stride != 0 or k != 0, a partial set among hit, gt_ptr and
+ * gt_idx, a wsum that is not 16-byte aligned.
+ * -------------------------------------------------------------------------*/
+int macr_group_hist(int U, const int32_t *row_ptr, const int32_t *ids, int stride, int k,
+                    const int32_t *gt_ptr, const int32_t *gt_idx, int n_items,
+                    const int32_t *group_of, int n_groups, const int32_t *item_weight,
+                    int32_t *cnt, int32_t *hit, long long *wsum, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Scores and full-catalogue positions of given (query, item) pairs (additive, abi 16).  The reference's test()
  * (macr_mf/train.py:224-251) materialises the whole (U, N) score matrix and ranklist_by_sorted keeps its first K columns;
  * these two calls answer for ANY pair -- a held-out item at position 900 as well as one at position 3 -- what that

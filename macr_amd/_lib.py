@@ -137,6 +137,7 @@ SIGNATURES = {
     "macr_item_exposure_workspace_bytes": (_z, [_i, _i, _i]),
     "macr_item_exposure": (_i, [_i, _i, _i, _p, _p, _p, _p, _i, _p, _i, _p, _p, _p, _p, _z, _p]),
     "macr_list_shift": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p]),
+    "macr_group_hist": (_i, [_i, _p, _p, _i, _i, _p, _p, _i, _p, _i, _p, _p, _p, _p, _p]),
     "macr_rank_positions_workspace_bytes": (_z, [_i, _ll, _i, _i]),
     "macr_score_pairs": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _ll, _p, _p]),
     "macr_rank_positions": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _ll, _p, _p, _z, _p]),

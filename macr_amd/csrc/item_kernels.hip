@@ -314,6 +314,70 @@ __global__ __launch_bounds__(kShiftQueries * kWave) void k_list_shift(int U, int
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Per row, a histogram of item groups and a weighted sum (macr_group_hist, MACR_CALIBRATION_REPORT): the popularity mix of
+// a user's list (ranking form: the first k slots of a row of stride `stride`) or of a user's profile (CSR form: the mask
+// CSR's row, any length).  One wave per row, kHistRows rows per workgroup.  The wave walks its row in chunks of 64 entries:
+// one coalesced read of the ids, one gather from group_of (and from item_weight) per lane, one LDS add into the wave's own
+// 64 group counters, and for a list with ground truth the binary search of k_metrics_mf and a second LDS add.  The weights
+// accumulate per lane in 64 bits and meet in one wave sum; the valid entries are counted by ballots.  The counters leave
+// through plain stores, lane g writing column g: every output element of a row is stored exactly once -- no global atomics,
+// nothing to zero, integer adds only, so the bytes do not depend on the order the lanes arrive in.
+constexpr int kHistRows = 4;
+constexpr int kHistGroups = 64;                      // n_groups <= 64: one counter per lane
+
+__global__ __launch_bounds__(kHistRows * kWave) void k_group_hist(int U, const int32_t *__restrict__ row_ptr,
+                                                                 const int32_t *__restrict__ ids, int stride, int k,
+                                                                 const int32_t *__restrict__ gt_ptr, const int32_t *__restrict__ gt_idx,
+                                                                 int n_items, const int32_t *__restrict__ group_of, int n_groups,
+                                                                 const int32_t *__restrict__ item_weight, int32_t *__restrict__ cnt,
+                                                                 int32_t *__restrict__ hit, long long *__restrict__ wsum) {
+    __shared__ int32_t bins[kHistRows][2][kHistGroups];              // per wave: group counts, group hits -- 2 KB
+    const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+    const long long u = (long long)blockIdx.x * kHistRows + wave;
+    const bool live = u < U;                          // (a wave past the last row still meets the barriers)
+    bins[wave][0][lane] = 0;
+    bins[wave][1][lane] = 0;
+    __syncthreads();
+    long long first = 0;
+    int len = 0, a = 0, n_gt = 0;
+    if (live) {
+        if (row_ptr) { first = row_ptr[u]; len = row_ptr[u + 1] - row_ptr[u]; }
+        else { first = u * stride; len = k; }
+        if (hit) { a = gt_ptr[u]; n_gt = gt_ptr[u + 1] - a; }
+    }
+    long long w = 0;
+    int n_valid = 0;
+    for (int p0 = 0; p0 < len; p0 += kWave) {          // (len is uniform over the wave: every lane meets the ballot)
+        const int p = p0 + lane;
+        const int32_t id = p < len ? ids[(size_t)first + p] : -1;
+        const bool valid = id >= 0 && id < n_items;   // -1 = unused slot; an id outside the catalogue is never counted
+        if (valid) {
+            const int g = group_of[id];
+            if (item_weight) w += item_weight[id];
+            if (g >= 0 && g < n_groups) {             // an item outside every group is in no column
+                atomicAdd(&bins[wave][0][g], 1);
+                if (hit && item_in_sorted(gt_idx + a, n_gt, id)) atomicAdd(&bins[wave][1][g], 1);
+            }
+        }
+        n_valid += __popcll(__ballot(valid));
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) w += __shfl_xor(w, o, kWave);
+    __syncthreads();
+    if (!live) return;
+    if (lane < n_groups) {
+        cnt[(size_t)u * n_groups + lane] = bins[wave][0][lane];
+        if (hit) hit[(size_t)u * n_groups + lane] = bins[wave][1][lane];
+    }
+    if (wsum && lane == 0) {
+        longlong2 out;
+        out.x = w;
+        out.y = n_valid;
+        reinterpret_cast<longlong2 *>(wsum)[u] = out;
+    }
+}
+
 }  // namespace macr
 
 using namespace macr;
@@ -333,6 +397,32 @@ extern "C" int macr_list_shift(int U, int K_base, int K_here, int k, const int32
     k_list_shift<<<blocks, kShiftQueries * kWave, 0, st>>>(U, K_base, K_here, k, n_items, rank_base, rank_here, gt_ptr, gt_idx,
                                                            per_user, entered, left);
     MACR_CHECK_LAUNCH("list_shift", st);
+    return MACR_OK;
+}
+
+extern "C" int macr_group_hist(int U, const int32_t *row_ptr, const int32_t *ids, int stride, int k, const int32_t *gt_ptr,
+                               const int32_t *gt_idx, int n_items, const int32_t *group_of, int n_groups, const int32_t *item_weight,
+                               int32_t *cnt, int32_t *hit, long long *wsum, void *stream) {
+    hipStream_t st = as_stream(stream);
+    MACR_REQUIRE(U >= 1, MACR_E_INVALID, "group_hist: U=%d", U);
+    MACR_REQUIRE(n_items > 0, MACR_E_INVALID, "group_hist: n_items=%d", n_items);
+    MACR_REQUIRE(n_groups >= 1 && n_groups <= kHistGroups, MACR_E_INVALID, "group_hist: n_groups=%d outside [1,%d]", n_groups, kHistGroups);
+    MACR_REQUIRE(ids, MACR_E_INVALID, "group_hist: ids is null");
+    MACR_REQUIRE(group_of, MACR_E_INVALID, "group_hist: group_of is null");
+    MACR_REQUIRE(cnt, MACR_E_INVALID, "group_hist: cnt is null");
+    if (row_ptr) {
+        MACR_REQUIRE(stride == 0 && k == 0, MACR_E_INVALID, "group_hist: row_ptr given (CSR form) with stride=%d k=%d, both must be 0", stride, k);
+    } else {
+        MACR_REQUIRE(k >= 1 && k <= stride, MACR_E_INVALID, "group_hist: k=%d outside [1, stride=%d] (ranking form)", k, stride);
+    }
+    MACR_REQUIRE((hit != nullptr) == (gt_ptr != nullptr) && (hit != nullptr) == (gt_idx != nullptr), MACR_E_INVALID,
+                 "group_hist: hit, gt_ptr and gt_idx are all given or all null (hit=%d gt_ptr=%d gt_idx=%d)", hit != nullptr,
+                 gt_ptr != nullptr, gt_idx != nullptr);
+    MACR_REQUIRE((reinterpret_cast<uintptr_t>(wsum) & 15) == 0, MACR_E_INVALID, "group_hist: wsum is not 16-byte aligned");
+    const unsigned blocks = (unsigned)(((long long)U + kHistRows - 1) / kHistRows);
+    k_group_hist<<<blocks, kHistRows * kWave, 0, st>>>(U, row_ptr, ids, stride, k, gt_ptr, gt_idx, n_items, group_of, n_groups,
+                                                       item_weight, cnt, hit, wsum);
+    MACR_CHECK_LAUNCH("group_hist", st);
     return MACR_OK;
 }
 

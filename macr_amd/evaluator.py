@@ -346,6 +346,43 @@ class Evaluator(object):
         counts = tuple(ops.item_counts(ids, self.gt, k, self.n_items, group_of, n_groups or 0) for ids in (entered, left))
         return per_user, entered, left, counts[0], counts[1]
 
+    # ------------------------------------------------------------------ calibration report (MACR_CALIBRATION_REPORT)
+    def list_calibration(self, kind, users_tab, user_ids, items_tab, k, w=None, wu=None, c=0.0, branch=None, group_of=None,
+                         n_groups=None, item_weight=None, with_base=False):
+        """The popularity mix of every query user's profile and of its list, for calibration.summarize:
+        (profile, here, base) on the device.  profile = (cnt, wsum) of the user's train list (the mask CSR, global ids):
+        int32 (U, n_groups) train items per group and int64 (U,2) {sum of item_weight, train items}; computed once per
+        evaluator and (group_of, n_groups, item_weight) and kept -- train lists never change.  here = (cnt, hit, wsum) of
+        the first k slots of the ranking an evaluation with the same arguments scores: list entries per group, those of
+        them in the user's ground truth, {sum of item_weight, list entries} (ops.group_hist).  base: the same triple for
+        the factual ranking (SCORE_NORMAL) with with_base, ranked by an evaluator of its own (_base_evaluator: this one's
+        seeds, policy state and graph cache stay as they were); else None.  group_of: n_items group ids, 0 .. n_groups-1
+        (n_groups None: max + 1); item_weight: n_items integers below 2^31 (the train counts) or None.
+        Ranked as item_exposure ranks (rank() without the -inf fill, `here` at the evaluator's last depth when that is
+        deeper than k) and counted on the MERGED rankings and the global-id train lists, which every rank holds: the same
+        bytes on one rank, on several and under item sharding, without a collective of its own."""
+        if group_of is None:
+            raise _lib.MacrError(_lib.E_INVALID, "list_calibration: group_of (one group id per item) is required")
+        k = int(k)
+        host = lambda a: None if a is None else np.asarray(a.cpu() if torch.is_tensor(a) else a).astype(np.int32)
+        group_of, item_weight = host(group_of), host(item_weight)
+        key = (group_of.tobytes(), n_groups, None if item_weight is None else item_weight.tobytes())
+        cached = getattr(self, "_calibration", None)
+        if cached is None or cached[0] != key:
+            groups, n = self._groups_on_device(group_of, n_groups)
+            weight = None if item_weight is None else self._groups_on_device(item_weight, 0)[0]
+            cnt, _, wsum = ops.group_hist(self.mask, groups, n, self.n_items, item_weight=weight)
+            cached = self._calibration = (key, groups, n, weight, (cnt, wsum))
+        _, groups, n, weight, profile = cached
+        depth = max(k, getattr(self, "_last_depth", 0))
+        _, here, _ = self.rank(kind, users_tab, user_ids, items_tab, depth, w, wu, c, fill_masked=False, branch=branch)
+        lists = [here]
+        if with_base:
+            lists.append(self._base_evaluator().rank(ops.SCORE_NORMAL, users_tab, user_ids, items_tab, k, w, wu, 0.0,
+                                                     fill_masked=False, branch=branch)[1])
+        out = [ops.group_hist(ids, groups, n, self.n_items, k=k, gt=self.gt, item_weight=weight) for ids in lists]
+        return profile, out[0], (out[1] if with_base else None)
+
     @staticmethod
     def _pairs_of(ids):
         """(ptr, idx, n_pairs): the non-negative entries of an (U,k) id array, row by row, as the pair CSR of rank_positions"""

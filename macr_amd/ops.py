@@ -644,6 +644,32 @@ def list_shift(rank_base, rank_here, gt, k, n_items, out=None):
     return per_user, entered, left
 
 
+def group_hist(rows, group_of, n_groups, n_items, k=None, gt=None, item_weight=None, with_wsum=True):
+    """Per row, the histogram of item groups and a weighted sum (macr_group_hist) -> (cnt, hit, wsum).  rows: a (U,K) int32
+    tensor of ranked ids (-1 = unused slot), read over its first k slots (k None: K), or a CSR over U rows (the evaluator's
+    mask CSR: the train lists).  group_of int32[n_items]; item_weight int32[n_items] or None; gt: the ground-truth CSR of the
+    same U rows or None.  cnt int32 (U, n_groups): valid entries (0 <= id < n_items) per group; hit: the same over the
+    entries whose id is in the row's ground truth (None without gt); wsum int64 (U,2) {sum of item_weight, valid entries}
+    (None with with_wsum=False).  Exact integers, every element overwritten."""
+    csr = isinstance(rows, CSR)
+    ids = rows.idx if csr else rows
+    U = rows.ptr.numel() - 1 if csr else rows.shape[0]
+    if (not csr and rows.dim() != 2) or (gt is not None and gt.ptr.numel() != U + 1):
+        raise MacrError(_lib.E_INVALID, "group_hist: a (U,K) ranking or a CSR, and a ground-truth CSR of the same %d rows expected" % U)
+    n_items, n_groups, dev = int(n_items), int(n_groups), ids.device
+    if group_of.numel() != n_items or (item_weight is not None and item_weight.numel() != n_items):
+        raise MacrError(_lib.E_INVALID, "group_hist: group_of and item_weight hold one value per item (%d)" % n_items)
+    stride, k = (0, 0) if csr else (rows.shape[1], rows.shape[1] if k is None else int(k))
+    cnt = torch.empty((max(U, 0), max(n_groups, 0)), dtype=_i32, device=dev)
+    hit = torch.empty_like(cnt) if gt is not None else None
+    wsum = torch.empty((max(U, 0), 2), dtype=torch.int64, device=dev) if with_wsum else None
+    check(_lib.lib().macr_group_hist(U, _ptr(rows.ptr, _i32) if csr else None, _ptr(ids, _i32), stride, k,
+                                     _ptr(gt.ptr, _i32) if gt is not None else None, _ptr(gt.idx, _i32) if gt is not None else None,
+                                     n_items, _ptr(group_of, _i32), n_groups, _ptr(item_weight, _i32, True), _ptr(cnt, _i32),
+                                     _ptr(hit, _i32, True), _ptr(wsum, torch.int64, True), _stream()))
+    return cnt, hit, wsum
+
+
 def score_pairs(kind, users_tab, user_ids, items, pairs, sig_u=None, sig_i=None, c=0.0, n_pairs=None):
     """fp32[n_pairs]: the score of every (query, item) pair of the CSR `pairs` over the queries (macr_score_pairs) -- bit for
     bit what score_matrix holds at [q, item]; NaN for an item outside the table.  n_pairs: pairs.ptr[-1] where the caller

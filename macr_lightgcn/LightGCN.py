@@ -29,10 +29,10 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from utility.helper import early_stopping, ensureDir          # noqa: E402
 from utility.batch_test import *                              # noqa: E402,F401,F403  (args, data_generator, test ...)
-from utility.branch_ranking import test, test_sweep, item_diagnostic, rank_diagnostic, exposure_diagnostic, shift_diagnostic           # noqa: E402,F811  (+ --test rubi1 / rubi2)
+from utility.branch_ranking import test, test_sweep, item_diagnostic, rank_diagnostic, exposure_diagnostic, shift_diagnostic, calibration_diagnostic           # noqa: E402,F811  (+ --test rubi1 / rubi2)
 from macr_amd.lightgcn import LightGCN as _LightGCN           # noqa: E402
 from macr_amd.mf import Session                               # noqa: E402
-from macr_amd import exposure, rank_report, shift_report                     # noqa: E402
+from macr_amd import calibration, exposure, rank_report, shift_report                     # noqa: E402
 
 logging.getLogger().setLevel(logging.INFO)
 
@@ -134,6 +134,8 @@ def main(sweep=False):
         raise SystemExit(shift_report.refusal("item-sharded"))
     if shift_report.enabled() and args.test == 'normal' and main_rank:
         print(shift_report.NOTHING_TO_COMPARE)
+    if calibration.enabled() == 2 and args.test == 'normal' and main_rank:
+        print(calibration.BASE_IS_THE_LIST)
 
     def say(text, end='\n'):
         if main_rank:
@@ -258,7 +260,7 @@ def main(sweep=False):
                         c, ret['recall'][0], ret['recall'][-1], ret['hr'][0], ret['hr'][-1], ret['ndcg'][0],
                         ret['ndcg'][-1])
             ret['hr'][0] = best_hr
-            if sweep and (args.out == 1 or rank_report.wanted() or exposure.enabled() or shift_report.enabled()):    # the diagnostics of the chosen c only (no hit at any c: the last one)
+            if sweep and (args.out == 1 or rank_report.wanted() or exposure.enabled() or shift_report.enabled() or calibration.enabled()):    # the diagnostics of the chosen c only (no hit at any c: the last one)
                 model.update_c(sess, c_values[-1] if best_c is None else best_c)
                 if args.out == 1:
                     item_diagnostic(sess, model, users_to_test, args.test)
@@ -268,6 +270,8 @@ def main(sweep=False):
                     exposure_diagnostic(sess, model, users_to_test, args.test)
                 if shift_report.enabled():
                     shift_diagnostic(sess, model, users_to_test, args.test)
+                if calibration.enabled():
+                    calibration_diagnostic(sess, model, users_to_test, args.test)
                 model.update_c(sess, c_values[-1])       # (what the loop left, and what a checkpoint records)
             if best_hr > best_c_hr:                      # config['best_c_epoch'] of the reference (:880)
                 best_c_hr, best_c_epoch = best_hr, epoch

@@ -10,7 +10,7 @@ import torch
 
 from utility import batch_test as _bt
 
-from macr_amd import exposure, ops, popularity, rank_report, sharding, shift_report
+from macr_amd import calibration, exposure, ops, popularity, rank_report, sharding, shift_report
 from macr_amd.eval_cache import EvaluatorCache
 from macr_amd.evaluator import Evaluator
 
@@ -54,6 +54,8 @@ def test(sess, model, users_to_test, drop_flag=False, train_set_flag=0, method="
         exposure_diagnostic(sess, model, users_to_test, method)
     if shift_report.enabled() and method != "normal":
         shift_diagnostic(sess, model, users_to_test, method)
+    if calibration.enabled():
+        calibration_diagnostic(sess, model, users_to_test, method)
     return ret
 
 
@@ -130,6 +132,29 @@ def shift_diagnostic(sess, model, users_to_test, method):
     if sharding.is_main():
         print(shift_report.format_line(shift_report.summarize(per_user.cpu().numpy(), e_rec.cpu().numpy(), e_hit.cpu().numpy(),
                                                               l_rec.cpu().numpy(), l_hit.cpu().numpy(), group_of, n_groups, k, depth)))
+
+
+def calibration_diagnostic(sess, model, users_to_test, method):
+    """MACR_CALIBRATION_REPORT=1: one line on whether the top-max(Ks) lists test() ranks with the same arguments (same score
+    kind, the model's current c -- after a sweep the chosen one) follow each user's own taste for popularity: the divergence
+    between the train-popularity mix of the user's profile and of its list (Jensen-Shannon, total variation), the popularity
+    lift of the lists over the profiles, and both with the recall for the niche, diverse and blockbuster-minded users
+    (macr_amd/calibration.py).  =2 adds the same figures of the factual ranking (--test normal) on the same users.  Every
+    rank ranks; the main rank prints."""
+    one_branch = method in _ITEM_BRANCH
+    evaluator, uid = (_evaluator_for if one_branch else _bt._evaluator_for)(model, users_to_test)
+    kind = ops.SCORE_RUBI if one_branch else _bt._METHODS[method]
+    tables = _popularity_tables()
+    k, n_groups = max(model.Ks), len(popularity.POINTS) + 1
+    ua, ia = model.propagated()
+    profile, here, base = evaluator.list_calibration(
+        kind, ua, uid, ia.contiguous(), k, model.w, model.w_user, model.rubi_c, branch=_branch(model, method) if one_branch else None,
+        group_of=tables["group_of"], n_groups=n_groups, item_weight=tables["train_counts"],
+        with_base=calibration.enabled() == 2 and kind != ops.SCORE_NORMAL)
+    if sharding.is_main():
+        host = lambda t: None if t is None else [x.cpu().numpy() for x in t]
+        print(calibration.format_line(calibration.summarize(host(profile), host(here), np.diff(evaluator.gt.ptr.cpu().numpy()), k,
+                                                            host(base))))
 
 
 def item_diagnostic(sess, model, users_to_test, method):

@@ -24,7 +24,7 @@ import torch
 from batch_test import *          # noqa: F401,F403  (args, data, Ks, BATCH_SIZE, ITEM_NUM, USER_NUM)
 from model import BPRMF, Session
 
-from macr_amd import exposure, ops, popularity, rank_report, shift_report
+from macr_amd import calibration, exposure, ops, popularity, rank_report, shift_report
 from macr_amd.evaluator import Evaluator
 from macr_amd.eval_cache import EvaluatorCache
 from macr_amd.metrics_host import (precision_at_k, dcg_at_k, ndcg_at_k, recall_at_k, hit_at_k,   # noqa: F401
@@ -76,6 +76,8 @@ def test(sess, model, test_users, batch_test_flag=False, model_type='o', valid_s
         exposure_diagnostic(sess, model, test_users, model_type, valid_set)
     if shift_report.enabled() and _MODEL_TYPES[model_type] != ops.SCORE_NORMAL:
         shift_diagnostic(sess, model, test_users, model_type, valid_set)
+    if calibration.enabled():
+        calibration_diagnostic(sess, model, test_users, model_type, valid_set)
     return ret
 
 
@@ -177,6 +179,32 @@ def shift_diagnostic(sess, model, test_users, model_type='rubi_both', valid_set=
                                                               l_rec.cpu().numpy(), l_hit.cpu().numpy(), group_of, n_groups, k, depth)))
 
 
+def calibration_diagnostic(sess, model, test_users, model_type='o', valid_set="test"):
+    """MACR_CALIBRATION_REPORT=1: one line on whether the top-max(Ks) lists test() ranks with the same arguments (same score kind,
+    the model's current c) follow each user's own taste for popularity -- the divergence between the train-popularity mix of
+    the user's profile and of its list (Jensen-Shannon, total variation), the popularity lift of the lists over the profiles,
+    and both with the recall for the niche, diverse and blockbuster-minded users (macr_amd/calibration.py).  =2 adds the same
+    figures of the factual ranking (--test normal) on the same users.  Counted on the merged rankings and the train lists:
+    every rank ranks (also under --row_shard 1), the main rank prints."""
+    from macr_amd import sharding
+    evaluator, uid = _evaluator_for(model, test_users, valid_set)
+    model.sync()
+    if "exposure" not in _n_test:
+        counts = popularity.train_counts(data.train_item_list, ITEM_NUM)
+        _n_test["exposure"] = (counts, popularity.item_groups(counts))
+    counts, group_of = _n_test["exposure"]
+    k, n_groups = max(Ks), len(popularity.POINTS) + 1
+    users_tab, ids = (model.query_rows(uid), None) if getattr(model, "sharded", False) else (model.user_embedding, uid)
+    with_base = calibration.enabled() == 2 and _MODEL_TYPES[model_type] != ops.SCORE_NORMAL
+    profile, here, base = evaluator.list_calibration(_MODEL_TYPES[model_type], users_tab, ids, model.item_embedding, k, model.w,
+                                                     model.w_user, model.rubi_c, group_of=group_of, n_groups=n_groups,
+                                                     item_weight=counts, with_base=with_base)
+    if sharding.is_main():
+        host = lambda t: None if t is None else [x.cpu().numpy() for x in t]
+        print(calibration.format_line(calibration.summarize(host(profile), host(here), np.diff(evaluator.gt.ptr.cpu().numpy()), k,
+                                                            host(base))))
+
+
 def test_sweep(sess, model, test_users, cs, model_type='rubi_both', valid_set="test"):
     """test() for every c of `cs` (the loop of macr_mf/tune.py:545-578) -> list of result dicts, one per c.  c only
     enters the score epilogue, so the values share the listing pass in groups of four (macr_score_topk_sweep)."""
@@ -268,6 +296,8 @@ def main(sweep=False):
         raise SystemExit(shift_report.refusal("--row_shard 1" if args.row_shard == 1 else "item-sharded"))
     if shift_report.enabled() and args.test != "rubi" and main_rank:
         print(shift_report.NOTHING_TO_COMPARE)
+    if calibration.enabled() == 2 and args.test != "rubi" and main_rank:
+        print(calibration.BASE_IS_THE_LIST)
 
     def say(text):
         if main_rank:
@@ -396,7 +426,7 @@ def main(sweep=False):
                 if ret['hit_ratio'][0] > best[0]:
                     best = (ret['hit_ratio'][0], ret['recall'][0], ret['precision'][0], ret['ndcg'][0], c)
             ret['hit_ratio'][0], ret['recall'][0], ret['precision'][0], ret['ndcg'][0] = best[:4]
-            if sweep and (args.out == 1 or rank_report.wanted() or exposure.enabled() or shift_report.enabled()):    # the diagnostics of the chosen c only (no hit at any c: the last one)
+            if sweep and (args.out == 1 or rank_report.wanted() or exposure.enabled() or shift_report.enabled() or calibration.enabled()):    # the diagnostics of the chosen c only (no hit at any c: the last one)
                 model.update_c(sess, best[4] if best[0] > 0 else c_values[-1])
                 if args.out == 1:
                     item_diagnostic(sess, model, users_to_test, rubi_type, args.valid_set)
@@ -406,6 +436,8 @@ def main(sweep=False):
                     exposure_diagnostic(sess, model, users_to_test, rubi_type, args.valid_set)
                 if shift_report.enabled():
                     shift_diagnostic(sess, model, users_to_test, rubi_type, args.valid_set)
+                if calibration.enabled():
+                    calibration_diagnostic(sess, model, users_to_test, rubi_type, args.valid_set)
                 model.update_c(sess, c_values[-1])   # (what the loop left, and what a checkpoint records)
             if best[0] > config['best_c_hr']:
                 config['best_c_hr'], config['best_c'], config['best_c_epoch'] = best[0], best[4], epoch
