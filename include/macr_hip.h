@@ -642,6 +642,8 @@ int macr_branch_sigmoid2(int d, const float *rows_a, const int32_t *idx_a, int n
  *              tables have moved far away from cost a repair round (below), never a wrong result.
  *   seed_out  (dev, may be NULL, may be seed_idx itself) int32[U*MACR_SEED_WIDTH] <- the best MACR_SEED_WIDTH candidates the
  *              selection saw per query, best first, -1 padded (the first K of them are out_idx): the next call's seed_idx.
+ *              (A block of queries that the exact fallback kernel ranked has exactly its K result ids there.  Not written by
+ *              the wide ranking, K > MACR_MAX_TOPK_FUSED, which takes no seeds.)
  *   stats     (dev, may be NULL) int32[2], written by the call: [0] blocks of 256 queries the repair round listed again,
  *              [1] 1 if the exact fallback kernel ran.  A caller that seeds uses [0] to tell stale seeds from good ones.
  *   out_val (dev) fp32 [n_splits*U*K], out_idx (dev) int32 [n_splits*U*K]:
@@ -672,6 +674,19 @@ int macr_branch_sigmoid2(int d, const float *rows_a, const int32_t *idx_a, int n
  * (k_tau_seed) instead of the sampling pass and its selection, and a listing pass that gives a
  * block of queries up to the repair round as soon as its lists grow faster than a usable
  * threshold allows (stale seeds).  No host synchronisation.
+ *
+ * NaN, infinite and overflowing scores -- for every K, filter and round, and for macr_score_topk_sweep:
+ *   - a (query, item) pair whose fp32 score (the k-ascending fma chain, then the kind's epilogue) is NaN is NO
+ *     CANDIDATE, exactly as if the query masked the item: a NaN element in a row, 0 * inf, inf - inf, a NaN branch factor;
+ *   - +inf and -inf are ordinary scores, whether an operand is infinite or finite products overflow: +inf ranks first,
+ *     an unmasked item scoring -inf is a candidate, counts, and leaves as (-inf, id); ties, also at +-inf, go to the
+ *     lower id;
+ *   - no NaN ever appears in out_val; a query with no candidate left has count 0 and K slots of (-inf, -1).
+ * A row with a NaN or infinite element, or whose squares overflow, has no norm for the reduced-precision filters to bound
+ * their error with: that query (every query, for an item row) is listed whole and ends in the exact kernel -- right, slow.
+ * macr_score_matrix still returns the NaN, macr_rank_positions gives such a pair position -1 and lets it precede nothing
+ * (one rule), and macr_topk_scores ranks the caller's matrix as it is (c_top_k_array_index has no rule for NaN).
+ * tests/nonfinite_cases.py states the rule on the oracle, tests/test_gpu_nonfinite.py holds the kernels to it.
  * -------------------------------------------------------------------------*/
 int    macr_score_topk_splits(int U, int n_local, int d);
 int    macr_score_topk_uses_seeds(int U, int n_local, int d);   /* 0: this shape lists every unmasked item, seed_idx is ignored */

@@ -118,7 +118,8 @@ __global__ __launch_bounds__(512, 2) void k_score_topk(
     const float *__restrict__ c_dev,
     const int32_t *__restrict__ mask_ptr, const int32_t *__restrict__ mask_idx, int item_offset, int K,
     int n_splits, float *__restrict__ out_val, int32_t *__restrict__ out_idx, uint32_t *shared_thr,
-    const int32_t *run_flag, int32_t *stats, const int32_t *__restrict__ only_blocks = nullptr) {
+    const int32_t *run_flag, int32_t *stats, const int32_t *__restrict__ only_blocks = nullptr,
+    int32_t *__restrict__ seed_out = nullptr) {
     // run_flag[0]: a candidate list overflowed twice (this kernel must run); run_flag[1]: user blocks the repair round re-listed
     if (stats && run_flag && blockIdx.x == 0 && threadIdx.x == 0) { stats[0] = run_flag[1]; stats[1] = run_flag[0]; }
     if (run_flag && *run_flag == 0) return;             // fallback launch: only when a candidate list overflowed
@@ -188,7 +189,9 @@ __global__ __launch_bounds__(512, 2) void k_score_topk(
     }
     // admission threshold = the user's current K-th best KEY (score, id); 0 = none yet.  Padding users never admit.
     float thr = q_ok ? -INFINITY : INFINITY;
-    int thr_id = -1;                               // with score == thr, only ids below thr_id rank higher
+    // with score == thr, only ids below thr_id rank higher.  While a query has no K-th key yet (thr = -inf) every id is: an
+    // unmasked item scoring -inf is a candidate like any other (tests/test_gpu_nonfinite.py: neg_inf_in_a_short_list)
+    int thr_id = q_ok ? INT_MAX : -1;
     float gthr = -INFINITY;                        // lower bound of the global K-th best score, from the other splits
 #ifdef MACR_ABL_NOADMIT
     thr = INFINITY;
@@ -224,7 +227,9 @@ __global__ __launch_bounds__(512, 2) void k_score_topk(
     // MFMAs of the same wave (an fp32 32x32x2 MFMA occupies the pipe for 64 cycles; ~8 VALU fit per gap).
     // Only the rare admission path (LDS atomics, compaction) runs outside the MFMA stream.
     struct Prev { int tile; int step; };
-    const float kNone = __builtin_nanf("");                // masked / out of range: every compare is false
+    // masked / out of range: every compare is false -- and so is every compare of a score that is NaN by itself: no candidate
+    // (the rule of include/macr_hip.h; tests/test_gpu_nonfinite.py sends every case it has through this kernel)
+    const float kNone = __builtin_nanf("");
 
     auto stage = [&](auto have_cur_t, auto have_prev_t, f32x16 &acc_cur, const f32x16 &acc_prev, int step, Prev prev) {
         constexpr bool have_cur = decltype(have_cur_t)::value;     // compile-time: keeps the MFMA stream branch-free
@@ -396,6 +401,9 @@ __global__ __launch_bounds__(512, 2) void k_score_topk(
             out_val[o] = key ? key_score(key) : -INFINITY;
             out_idx[o] = key ? key_id(key) : -1;
         }
+        // the caller's next seeds (macr_score_topk seed_out: "the first K of them are out_idx"): what the selection left there came
+        // from lists that were cut.  This kernel keeps K per query: exactly K seeds, -1 padded (32 = MACR_SEED_WIDTH, defined below)
+        if (seed_out && n_splits == 1 && lane < 32) seed_out[(size_t)qq * 32 + lane] = (lane < K && key) ? key_id(key) : -1;
     }
 }
 
@@ -430,7 +438,8 @@ inline size_t score_topk_smem_bytes() {
 // back to k_score_topk, which is exact for any input.
 //
 // Masked (train) items and the tail of the last tile are poisoned at accumulator INIT (NaN + x = NaN,
-// NaN >= tau is false, max(m, NaN) = m): nothing per element.  Which items of a tile a user masks is one
+// NaN >= tau is false, max(m, NaN) = m): nothing per element.  A score that is NaN by itself fails the same tests: it is no
+// candidate either (include/macr_hip.h; tests/test_gpu_nonfinite.py).  Which items of a tile a user masks is one
 // 32-bit word of a (tile, user) bitmap that k_mask_bits scatters from the CSR lists once per call; the
 // word is prefetched with the tile (a CSR cursor costs a dependent load whenever it advances).
 // A operand in LDS as [item][h][t] (k = 2t+h), row stride D+4: a lane's whole k-row is contiguous
@@ -943,7 +952,8 @@ __device__ __forceinline__ float filter_margin(int d, float unorm, float qmax, f
 //   * |x| > 65504 (a query row scaled by 1 / sig_u for DIRECT_MINUS_BOTH with sig_u below ~1e-5, an absurd embedding or c):
 //     the operand is CLAMPED (no inf, hence no NaN, enters an accumulator) and its norm reported as +inf: an infinite
 //     margin lists everything for that query (for every query when an item row did it), the lists overflow and the exact
-//     kernel ranks -- right, slow, and not a case a trained model produces.
+//     kernel ranks -- right, slow, and not a case a trained model produces (tests/test_gpu_nonfinite.py: inf_*, overflow_*;
+//     a NaN operand becomes -65504 and its row's norm NaN, reported as +inf all the same: nan_*).
 //   * RUBI_BOTH lists acc'' * sig_u: off by sig_u times the accumulator's margin -- the thresholds, the listing test and
 //     k_select_b scale the margin by sig_u there (a query with sig_u = 0.01 has scores, and score gaps, a hundred times smaller).
 // filter_rel_h(d) = 1.001 * 2^-10 + 8 d 2^-24: d = 32: 9.93e-4, 64: 1.008e-3, 128: 1.039e-3, 256: 1.100e-3.
@@ -955,12 +965,16 @@ constexpr float kHalfMax = 65504.f;
 __device__ __forceinline__ float filter_margin_h(int d, float unorm, float qmax, float c) {
     const float b = unorm * qmax * 1.0001f;
     const float m = filter_rel_h(d) * b + kFilterAbs * (b + fabsf(c)) + kHalfTiny * (sqrtf((float)d) * (unorm + qmax) + 2.0f) + 1e-37f;
-    return m == m ? m : INFINITY;            // (inf * 0: a flagged query against an all-zero catalogue)
+    return m == m ? m : INFINITY;            // (inf * 0: a flagged query against an all-zero catalogue; tests/test_gpu_nonfinite.py runs the infinite margins)
 }
 // the margin of the filter in use: half != 0 = the fp16 filter
 __device__ __forceinline__ float filter_margin_of(int half, int d, float unorm, float qmax, float c) {
     return half ? filter_margin_h(d, unorm, qmax, c) : filter_margin(d, unorm, qmax, c);
 }
+// A threshold less `m` (a margin, already times its factors).  A query without a bound -- an infinite margin, or NaN where a
+// factor of it is -- gets -inf, "list everything", whatever the threshold: a K-th score of +inf (infinite or overflowing
+// products) must not turn into inf - inf = NaN, a threshold no score passes (tests/test_gpu_nonfinite.py: overflow_*, inf_*)
+__device__ __forceinline__ float tau_less_margin(float tau, float m) { return m < INFINITY ? tau - m : -INFINITY; }
 __device__ __forceinline__ uint32_t f16_rne_bits(float f) {            // round to nearest even, clamped to the finite range
     f = fminf(fmaxf(f, -kHalfMax), kHalfMax);
     const _Float16 hv = (_Float16)f;
@@ -1012,24 +1026,29 @@ __device__ __forceinline__ void bf16_prep_block(int blk, int U, int n_local, con
     for (int t = 0; t < kPrepTrips; ++t) {
         const bool is_item = row[t] < n_local;
         const long long q = row[t] - n_local;
-        float sq = 0.f;
+        // the norm first: a row without a bound -- a NaN or infinite element, or squares that overflow: |row| = +inf, the margin
+        // of that query (of every query, for an item row) infinite, everything listed and re-scored -- leaves as ZEROS.  Its
+        // products have no say under an infinite margin, and no inf (whose low part is inf - inf = NaN) or overflowing product
+        // enters an accumulator, where a NaN would fail the listing test that -inf is meant to pass
+        // (tests/test_gpu_nonfinite.py: nan_*, inf_*, overflow_* under the bf16 filter)
+        float sq = (is_item || q < U) ? dot4(a[t], a[t]) + dot4(b[t], b[t]) : 0.f;
+        sq = group_sum<LPRB>(sq);
+        float nrm = sqrtf(sq) * 1.0001f;                      // (rounded up: the margin must not be short)
+        const bool bounded = nrm < INFINITY;
+        if (!bounded) nrm = INFINITY;
         if (is_item || q < U) {
             const float x[8] = {a[t].x, a[t].y, a[t].z, a[t].w, b[t].x, b[t].y, b[t].z, b[t].w};
             uint32_t hi[8], lo[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                hi[k] = bf16_rne_bits(x[k]);
-                lo[k] = bf16_rne_bits(x[k] - __uint_as_float(hi[k] << 16));       // (x - hi is exact in fp32)
+                hi[k] = bounded ? bf16_rne_bits(x[k]) : 0u;
+                lo[k] = bounded ? bf16_rne_bits(x[k] - __uint_as_float(hi[k] << 16)) : 0u;       // (x - hi is exact in fp32)
             }
             // row layout: hi[D] then lo[D]
             uint4 *dst = is_item ? items_bf + (size_t)row[t] * 2 * LPRB : users_bf + (size_t)q * 2 * LPRB;
             dst[sub] = make_uint4(hi[0] | (hi[1] << 16), hi[2] | (hi[3] << 16), hi[4] | (hi[5] << 16), hi[6] | (hi[7] << 16));
             dst[LPRB + sub] = make_uint4(lo[0] | (lo[1] << 16), lo[2] | (lo[3] << 16), lo[4] | (lo[5] << 16), lo[6] | (lo[7] << 16));
-            sq = dot4(a[t], a[t]) + dot4(b[t], b[t]);
         }
-        sq = group_sum<LPRB>(sq);
-        float nrm = sqrtf(sq) * 1.0001f;                      // (rounded up: the margin must not be short)
-        if (!(nrm == nrm)) nrm = INFINITY;                    // a NaN row: margin +inf, everything of that user is listed / re-scored
         if (!is_item && q < U && sub == 0) unorm[q] = nrm;
         if (is_item) m = fmaxf(m, nrm);
     }
@@ -1204,7 +1223,7 @@ __global__ __launch_bounds__(StreamGroupsB<D>::THREADS, D <= 64 ? 4 : 2) void k_
         su[g] = (score_uses_sig_u(KIND) && q_ok[g]) ? sig_u[q[g]] : 1.0f;
         // listing test: score_bf16 >= tau - margin (NaN = never: padding users)
         tau_s[g] = __builtin_nanf("");
-        if (q_ok[g]) tau_s[g] = tau[q[g]] - 1.01f * filter_margin(D, unorm[q[g]], qmax, c);
+        if (q_ok[g]) tau_s[g] = tau_less_margin(tau[q[g]], 1.01f * filter_margin(D, unorm[q[g]], qmax, c));
         // the test on the raw product (filter_y): acc >= fma(fx, Y_i, fz)
         fx[g] = 0.f; fz[g] = tau_s[g];
         if (KIND == MACR_SCORE_RUBI_BOTH) { fx[g] = tau_s[g] / su[g]; fz[g] = c; }
@@ -1531,7 +1550,13 @@ __device__ __forceinline__ void bf16_prep_c_block(int blk, int U, int n_local, c
         const bool is_item = row[t] < n_local, is_pad = row[t] >= n_local && row[t] < n_pad;
         const long long q = row[t] - n_pad;
         const bool is_user = q >= 0 && q < U;
-        float sq = 0.f, clamped = 0.f;
+        // (the norm first, of the row as given, not as scaled.  bf16 copies: a row without a bound leaves as zeros -- see
+        // bf16_prep_block; the fp16 copies are clamped to the finite range instead and need no such thing)
+        float sq = (is_item || is_user || is_pad) ? dot4(a[t], a[t]) + dot4(b[t], b[t]) : 0.f, clamped = 0.f;
+        sq = group_sum<LPRB>(sq);
+        float nrm = sqrtf(sq) * 1.0001f;
+        const bool bounded = nrm < INFINITY;                  // NaN or +inf: margin +inf, everything of that query is listed / re-scored
+        if (!bounded) nrm = INFINITY;
         if (is_item || is_user || is_pad) {
             const float x[8] = {a[t].x * scale[t], a[t].y * scale[t], a[t].z * scale[t], a[t].w * scale[t],
                                 b[t].x * scale[t], b[t].y * scale[t], b[t].z * scale[t], b[t].w * scale[t]};
@@ -1543,8 +1568,8 @@ __device__ __forceinline__ void bf16_prep_c_block(int blk, int U, int n_local, c
                     lo[k] = 0u;
                     if (!is_pad && fabsf(x[k]) > kHalfMax) clamped = 1.0f;
                 } else {
-                    hi[k] = is_pad ? 0u : bf16_rne_bits(x[k]);
-                    lo[k] = is_pad ? 0u : bf16_rne_bits(x[k] - __uint_as_float(hi[k] << 16));
+                    hi[k] = (is_pad || !bounded) ? 0u : bf16_rne_bits(x[k]);
+                    lo[k] = (is_pad || !bounded) ? 0u : bf16_rne_bits(x[k] - __uint_as_float(hi[k] << 16));
                 }
             }
             const uint4 vh = make_uint4(hi[0] | (hi[1] << 16), hi[2] | (hi[3] << 16), hi[4] | (hi[5] << 16), hi[6] | (hi[7] << 16));
@@ -1571,11 +1596,7 @@ __device__ __forceinline__ void bf16_prep_c_block(int blk, int U, int n_local, c
                     }
                 }
             }
-            sq = dot4(a[t], a[t]) + dot4(b[t], b[t]);         // (of the row as given, not as scaled)
         }
-        sq = group_sum<LPRB>(sq);
-        float nrm = sqrtf(sq) * 1.0001f;
-        if (!(nrm == nrm)) nrm = INFINITY;
         if (HALF && group_sum<LPRB>(clamped) > 0.f) nrm = INFINITY;     // an operand outside fp16's range: no bound for this row
         if (is_user && sub == 0) unorm[q] = nrm;
         if (is_item) m = fmaxf(m, nrm);
@@ -1703,7 +1724,7 @@ __global__ __launch_bounds__(512, D <= 64 ? 4 : 2) void k_score_stream_c(
     const bf16x8 bext = ones.v;
     // listing test: v_bf16 >= tau - margin  <=>  acc'' >= (tau - margin) / fu   (fu > 0; NaN = never: padding queries)
     float tau_s = __builtin_nanf("");
-    if (q_ok) tau_s = tau[q] - 1.01f * filter_margin(D, unorm[q], qmax, c);
+    if (q_ok) tau_s = tau_less_margin(tau[q], 1.01f * filter_margin(D, unorm[q], qmax, c));
     float thr = tau_s / fu;
     if (KIND == MACR_SCORE_RUBI_BOTH && tiny) thr = q_ok ? -INFINITY : thr;       // (scores of the order of sig_u: everything is a candidate)
     uint64_t *my_list = lists + ((size_t)split * rl.stride + ((REPAIR && rl.compact) ? ubv * kUsersPerBlock + uslot : (q_ok ? q : 0))) * cap;
@@ -2159,7 +2180,7 @@ __global__ __launch_bounds__(StreamCfgH<D>::THREADS, D <= 64 ? 4 : 2) void k_sco
         fu[g] = query_factor_h<KIND>(su);                     // listed score = acc'' * fu
         bext[g] = bias_query_unit_h<KIND>(su, KIND != MACR_SCORE_NORMAL && h == 0);
         float tau_s = __builtin_nanf("");
-        if (q_ok) tau_s = tau[q] - 1.01f * filter_margin_h(D, unorm[q], qmax, c) * fu[g];      // (the margin of acc'' times the score's outer factor)
+        if (q_ok) tau_s = tau_less_margin(tau[q], 1.01f * filter_margin_h(D, unorm[q], qmax, c) * fu[g]);      // (the margin of acc'' times the score's outer factor)
         thr[g] = tau_s / fu[g];
         if (tiny) thr[g] = q_ok ? -INFINITY : thr[g];        // (scores of the order of sig_u: everything is a candidate)
         my_list[g] = (uint32_t)((size_t)split * rl.stride + ((REPAIR && rl.compact) ? ubv * kUsersPerBlock + uslot : (q_ok ? q : 0)));
@@ -2475,7 +2496,7 @@ __global__ __launch_bounds__(512, D <= 64 ? 4 : 2) void k_score_stream_bs(
 #pragma unroll
     for (int g = 0; g < NC; ++g) {
         c_g[g] = g < sw.n_c ? c_dev[g] : 0.f;
-        tau_g[g] = (g < sw.n_c && q_ok) ? sw.tau[g][q] - 1.01f * filter_margin(D, un, qmax, c_g[g]) : __builtin_nanf("");
+        tau_g[g] = (g < sw.n_c && q_ok) ? tau_less_margin(sw.tau[g][q], 1.01f * filter_margin(D, un, qmax, c_g[g])) : __builtin_nanf("");
         fx[g] = 0.f; fz[g] = tau_g[g];
         if (KIND == MACR_SCORE_RUBI_BOTH) { fx[g] = tau_g[g] / su; fz[g] = c_g[g]; }
         else if (KIND == MACR_SCORE_RUBI) { fx[g] = tau_g[g]; fz[g] = c_g[g]; }
@@ -2748,7 +2769,7 @@ __global__ __launch_bounds__(512, D <= 64 ? 4 : 2) void k_score_sample_b(
 }
 
 constexpr int kSeedWidth = MACR_SEED_WIDTH;
-static_assert(kSeedWidth == 32, "one 32-lane half per user");
+static_assert(kSeedWidth == 32, "one 32-lane half per user (and k_score_topk's seed_out rows)");
 template <int D, int KIND>
 __device__ __forceinline__ void tau_seed_block(int blk, int U, int n_local, const float *__restrict__ users_tab,
                                                const int32_t *__restrict__ user_ids, const float *__restrict__ items,
@@ -2782,7 +2803,7 @@ __device__ __forceinline__ void tau_seed_block(int blk, int U, int n_local, cons
         }
         v = acc;
         if (score_uses_sig_i(KIND)) v = score_epilogue<KIND>(v, c, sig_i[it], score_uses_sig_u(KIND) ? sig_u[q] : 1.0f);
-        ok = v == v;                                      // NaN: no bound from this seed
+        ok = v == v;                                      // NaN: no bound from this seed (tests/test_gpu_nonfinite.py, seeded: the seeds of the undamaged tables)
     }
     // rotation inside the half: drop repetitions of an earlier lane's id, then rank the good seeds by score
     const int half = threadIdx.x & 32;
@@ -2915,7 +2936,7 @@ __global__ __launch_bounds__(64 * kSelWaves) void k_tau(int U, int n_splits, int
     }
     // maxima of bf16 scores (k_score_sample_b): K items score >= t_out - margin in fp32
     // (mscale: the fp16 filter states its margin on the accumulator; a score that leaves it times sig_u -- RUBI_BOTH -- is off by sig_u times that)
-    if (unorm) t_out -= 1.01f * filter_margin_of(half, d_filter, unorm[q], __uint_as_float(*qmax_bits), c_dev ? *c_dev : c_val) * (mscale ? mscale[q] : 1.0f);
+    if (unorm) t_out = tau_less_margin(t_out, 1.01f * filter_margin_of(half, d_filter, unorm[q], __uint_as_float(*qmax_bits), c_dev ? *c_dev : c_val) * (mscale ? mscale[q] : 1.0f));
     if (lane == 0) tau[q] = REPAIR ? fmaxf(tau[q], t_out) : t_out;
 }
 
@@ -3140,7 +3161,7 @@ __device__ __forceinline__ uint64_t exact_key(int q, int id, const float *__rest
                                               const float *__restrict__ items, const float *__restrict__ sig_u,
                                               const float *__restrict__ sig_i, float c, int item_offset) {
     const float v = exact_score<D, KIND>(q, id - item_offset, users_tab, user_ids, items, sig_u, sig_i, c);     // (common.hpp)
-    return v == v ? make_key(v, id) : 0ull;                   // (a NaN score is no candidate: the fp32 listing test fails on it too)
+    return v == v ? make_key(v, id) : 0ull;                   // (a NaN score is no candidate: the fp32 listing test fails on it too; tests/test_gpu_nonfinite.py)
 }
 
 // A query whose 64 best bf16 scores do not settle the top (k_select_b): every listed candidate gets its exact key, in
@@ -3525,7 +3546,8 @@ __global__ __launch_bounds__(256) void k_topk_scores_wide(const float *__restric
                                                           int32_t *__restrict__ out_idx, float *__restrict__ out_val,
                                                           const uint32_t *__restrict__ mask_bits, int mask_stride, int q0,
                                                           int id_offset, int out_stride, int out_off,
-                                                          const uint64_t *__restrict__ below, uint64_t *__restrict__ last_key) {
+                                                          const uint64_t *__restrict__ below, uint64_t *__restrict__ last_key,
+                                                          int drop_nan) {
     __shared__ uint64_t s_keys[4][kWideCap];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int row = blockIdx.x * 4 + wid;
@@ -3538,7 +3560,9 @@ __global__ __launch_bounds__(256) void k_topk_scores_wide(const float *__restric
     const uint64_t ceil_key = bounded ? below[row] : 0ull;
     for (int base = 0; base < cols; base += kWave) {
         const int cidx = base + lane;
-        uint64_t key = cidx < cols ? make_key(src[cidx], cidx) : 0ull;
+        const float v = cidx < cols ? src[cidx] : 0.f;
+        uint64_t key = cidx < cols ? make_key(v, cidx) : 0ull;
+        if (drop_nan && !(v == v)) key = 0ull;                    // macr_score_topk's rule: a NaN score is no candidate
         if (mask_bits && cidx < cols && ((mask_bits[(size_t)(cidx >> 5) * mask_stride + q0 + row] >> (cidx & 31)) & 1u)) key = 0ull;
         if (bounded && key >= ceil_key) key = 0ull;               // ranked by an earlier round (ceil_key 0: nothing is left)
         admit_wide(keys, cnt, thr_key, key, K);
@@ -4406,7 +4430,7 @@ static int score_topk_impl(int mode, int filter, int score_kind, int U, int n_lo
                                                 items, sig_u ? sig_u + q0 : nullptr, sig_i, c, c_dev, scores)));
             MACR_CHECK_LAUNCH("score_matrix", st);
             k_topk_scores_wide<<<(nq + 3) / 4, 256, 0, st>>>(scores, n_local, nq, K, out_idx + (size_t)q0 * K, out_val + (size_t)q0 * K,
-                                                             mask_bits, U, q0, item_offset, K, 0, nullptr, nullptr);
+                                                             mask_bits, U, q0, item_offset, K, 0, nullptr, nullptr, 1);
             MACR_CHECK_LAUNCH("topk_scores", st);
         }
         if (n_splits > 1) {
@@ -4639,7 +4663,7 @@ static int score_topk_impl(int mode, int filter, int score_kind, int U, int n_lo
         kern<<<ublocks * n_splits, 512, smem_old, st>>>(U, n_local, users_tab, user_ids, items, sig_u, sig_i, c, c_dev,
                                                         mask_ptr, mask_idx, item_offset, K, n_splits, out_val, out_idx,
                                                         n_splits > 1 ? ws.shared_thr : nullptr, force_fallback ? nullptr : ws.overflow,
-                                                        stats, force_fallback ? nullptr : ws.blk_flag);
+                                                        stats, force_fallback ? nullptr : ws.blk_flag, seed_out);
     });
     MACR_CHECK_LAUNCH("score_topk", st);
     return MACR_OK;
@@ -4872,7 +4896,7 @@ extern "C" int macr_score_topk_sweep(int score_kind, int filter, int U, int n_lo
         for (int g = 0; g < n_c; ++g)
             kern<<<ublocks, 512, smem_old, st>>>(U, n_local, users_tab, user_ids, items, sig_u, sig_i, 0.f, c_dev + g, mask_ptr, mask_idx,
                                                  item_offset, K, 1, out_val + (size_t)g * U * K, out_idx + (size_t)g * U * K,
-                                                 nullptr, force_fallback ? nullptr : ws[g].overflow, nullptr, nullptr);
+                                                 nullptr, force_fallback ? nullptr : ws[g].overflow, nullptr, nullptr, nullptr);
     });
     MACR_CHECK_LAUNCH("score_topk", st);
     return MACR_OK;
@@ -5000,7 +5024,7 @@ extern "C" int macr_topk_scores(const float *scores, int cols, int rows, int K, 
     MACR_REQUIRE(cols > 0 && rows > 0, MACR_E_INVALID, "topk_scores: cols=%d rows=%d", cols, rows);
     MACR_REQUIRE(K >= 1, MACR_E_INVALID, "topk_scores: K=%d", K);
     if (K <= MACR_MAX_TOPK_FUSED) k_topk_scores<<<(rows + 3) / 4, 256, 0, st>>>(scores, cols, rows, K, out_idx, out_val);
-    else if (K <= MACR_MAX_TOPK) k_topk_scores_wide<<<(rows + 3) / 4, 256, 0, st>>>(scores, cols, rows, K, out_idx, out_val, nullptr, 0, 0, 0, K, 0, nullptr, nullptr);
+    else if (K <= MACR_MAX_TOPK) k_topk_scores_wide<<<(rows + 3) / 4, 256, 0, st>>>(scores, cols, rows, K, out_idx, out_val, nullptr, 0, 0, 0, K, 0, nullptr, nullptr, 0);
     else {
         // c_top_k_array_index takes any top_k (tools.h:13-22): rounds of 128 positions, each bounded by the last key of the one before
         MACR_REQUIRE(workspace && workspace_bytes >= macr_topk_scores_workspace_bytes(rows, K), MACR_E_WORKSPACE,
@@ -5010,7 +5034,7 @@ extern "C" int macr_topk_scores(const float *scores, int cols, int rows, int K, 
         for (int off = 0; off < K; off += MACR_MAX_TOPK) {
             const int k = std::min(MACR_MAX_TOPK, K - off);
             k_topk_scores_wide<<<(rows + 3) / 4, 256, 0, st>>>(scores, cols, rows, k, out_idx, out_val, nullptr, 0, 0, 0, K, off,
-                                                                off ? last : nullptr, last);
+                                                                off ? last : nullptr, last, 0);
             MACR_CHECK_LAUNCH("topk_scores", st);
         }
     }
